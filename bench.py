@@ -7,11 +7,26 @@ HBM, 1 MiB fixed blocks, all candidates 0..8 evaluated per block, MDL winner emi
 One step = one full compress of the rank's batch from HBM to a device payload arena
 (+ for N > 1 the RCCL gather of every rank's payloads and method ids to rank 0).
 Weak scaling: per-GPU work is fixed; value = all ranks' input bytes / max-over-ranks time.
-The timed steps run with kernel timing OFF; a separate pass of --kt-steps steps records
-HIP events around every launch (per-kernel durations), and at N=1 one more step runs
-with the streams serialised (each kernel's solo duration).
+The timed steps run with kernel timing OFF.
 
-Also reported:
+A plain run (python bench.py --gpus 1 --steps K --warmup W) does only what the headline
+needs: it generates the input, warms up, times the K steps, writes the outputs of the
+last timed step if --dump-outputs DIR is given, and prints the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ratio and winner histogram).  Everything
+below runs only with --full: a separate pass of --kt-steps steps records HIP events around
+every launch (per-kernel durations), and at N=1 one more step runs with the streams
+serialised (each kernel's solo duration).
+
+--dump-outputs DIR  what a caller of the timed path receives from its last timed step, as
+                DIR/<name>.npy (rank r > 0 of a multi-GPU run: <name>_rank<r>.npy): sizes
+                (blocks x candidates, float64), method (winner id per block, float64), off
+                (payload offsets, blocks + 1, float64), payload_checksums (per block: sum of the
+                payload bytes and sum of byte x (position in the block's payload + 1), float64,
+                exact) and payload (the arena bytes [0, off[-1]) as float32: all of them up to
+                12 Mi bytes, else a fixed seeded sample of 8 Mi positions, sorted).  The
+                input is seeded, so two builds run with the same arguments compare file by file.
+
+Also reported (--full):
   roofline      the critical path: the SORT STREAM (Lyndon -> omega-order sort -> BBWT
                 gather -> MTF + Rice sizes; the LZ77 parse runs beside it on the index
                 stream and is hidden).  achieved = SURVEY §8d contract bytes of that stream
@@ -32,7 +47,7 @@ Also reported:
   --strong      makes config 4 the headline (scaling "strong"): every rank encodes its
                 round-robin shard of the one 256 MiB stream; value = 256 MiB / time.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 via
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; for N > 1 via
 python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 (the launcher only sets RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*: this process uses no PyTorch —
 device memory, the RCCL communicator, barriers and reductions all go through libkolm_hip.so's
@@ -208,6 +223,32 @@ def check_blocks(g, sizes, method, arena_host, off, ncand, wkey, shakey):
     return ok
 
 
+DUMP_WHOLE_MAX = 12 << 20  # payload bytes written whole (as float32: 48 MiB)
+DUMP_SAMPLE = 8 << 20      # sampled positions of a longer payload (32 MiB)
+DUMP_SEED = 20251212
+
+
+def dump_outputs(dirname, rank, sizes, method, off, payload: bytes):
+    """The outputs of one kolm_encode_blocks_device call as DIR/<name>.npy (module doc).
+    uint32 / uint64 values below 2^53 and byte sums of a block are exact in float64."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    pay = np.frombuffer(payload, dtype=np.uint8)
+    o = off.astype(np.int64)
+    chk = np.zeros((len(o) - 1, 2), np.float64)
+    for i in range(len(o) - 1):
+        b = pay[o[i]:o[i + 1]].astype(np.float64)
+        chk[i, 0] = b.sum()
+        chk[i, 1] = np.dot(b, np.arange(1, b.size + 1, dtype=np.float64))
+    if pay.size > DUMP_WHOLE_MAX:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, pay.size, DUMP_SAMPLE))
+        pay = pay[pos]
+    for name, arr in (("sizes", sizes.astype(np.float64)), ("method", method.astype(np.float64)),
+                      ("off", off.astype(np.float64)), ("payload_checksums", chk),
+                      ("payload", pay.astype(np.float32))):
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), arr)
+
+
 COMM = None  # kolm.parallel.Comm (RCCL behind the C ABI) when WORLD_SIZE > 1
 
 
@@ -230,6 +271,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mib", type=int, default=256, help="input MiB per GPU")
     ap.add_argument("--bs", type=int, default=1 << 20, help="block size")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (parity against the fixtures, kernel-timed and "
+                         "serialised passes, roofline, decode, ids 0..9, CDC, v2_new, configs 2/4/5, host API, "
+                         "CPU baseline); the options below select among them and are ignored without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (see the module doc)")
     ap.add_argument("--kt-steps", type=int, default=2, help="steps of the kernel-timed pass (HIP events per launch)")
     ap.add_argument("--no-serial-pass", action="store_true", help="skip the serialised-streams step (N=1)")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of oracle CPU work (N=1)")
@@ -254,6 +301,8 @@ def main():
                     help="timed steps of the config-4 leg (N=1: the 8-GPU shard, blocks i = 0 mod 8 of the stream; "
                          "N>1: the whole config, --mib MiB total round-robin); 0 = skip")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -266,16 +315,16 @@ def main():
     n = a.mib << 20
     t = time.time()
     stream0 = None  # rank 0's stream: the config-4 data (256 MiB total, sharded)
-    if a.strong or a.c4_steps > 0:
+    if a.strong or (a.full and a.c4_steps > 0):
         stream0 = datagen.enwik_like(n, seed=datagen.ENWIK_SEED)
     data = stream0 if rank == 0 and stream0 is not None else datagen.enwik_like(n, seed=datagen.ENWIK_SEED + rank)
     log(rank, f"[bench] generated {a.mib} MiB per rank in {time.time() - t:.1f}s")
     nb_stream = (n + a.bs - 1) // a.bs
-    golden_full = load_golden_stream(rank, n, a.bs)
+    golden_full = load_golden_stream(rank, n, a.bs) if a.full else None
     if a.strong:  # this rank's round-robin shard of rank 0's stream is the workload
         mine = list(range(rank, nb_stream, world))
         data = b"".join(stream0[i * a.bs:(i + 1) * a.bs] for i in mine)
-        golden_full = golden_subset(load_golden_stream(0, n, a.bs), mine)
+        golden_full = golden_subset(load_golden_stream(0, n, a.bs), mine) if a.full else None
         n = len(data)
 
     L = _lib.load()
@@ -342,6 +391,41 @@ def main():
     ms_step = el / a.steps * 1e3
     ntot = sum_all(n, world)  # whole-job input bytes per step
     value = ntot * a.steps / el / MB
+
+    def headline():
+        return {
+            "metric": "compress MB/s at fixed block size, bit-exact vs reference; 1/2/4/8-GPU scaling",
+            "value": round(value, 2), "unit": "MB/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(ms_step, 2), "higher_is_better": True, "scaling": "strong" if a.strong else "weak",
+            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "config": {"workload": ("BASELINE config 4: enwik-style synthetic text (kolm.datagen.enwik_like, seed "
+                                    f"20251212), {a.mib} MiB TOTAL in {a.bs >> 20} MiB blocks sharded round-robin "
+                                    f"over {world} GPU(s), resident in HBM, candidates 0..8 + MDL, payloads emitted "
+                                    "in HBM" + (", RCCL gather to rank 0" if world > 1 else "")) if a.strong else
+                                   ("enwik-style synthetic text (kolm.datagen.enwik_like, seed 20251212+rank), "
+                                    f"{a.mib} MiB per GPU resident in HBM, {a.bs >> 20} MiB fixed blocks, "
+                                    "candidates 0..8 + MDL, payloads emitted in HBM"
+                                    + (", RCCL gather to rank 0" if world > 1 else "")),
+                       "block_size": a.bs, "bytes_per_gpu": n, "blocks_per_gpu": nb,
+                       "parallelism": f"block-shard x{world}"},
+        }
+
+    # ---- the outputs of the last timed step, for output-by-output comparison of two builds ----
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, sizes, method, off, arena.download(int(off[-1])))
+
+    if not a.full:  # a plain run ends here: the headline alone
+        if rank == 0:
+            out = headline()
+            out.update({"roofline": None, "cpu_baseline": None,
+                        "detail": {"ratio": round(float(off[-1]) / n, 4),
+                                   "methods": np.bincount(method, minlength=10).tolist(),
+                                   "note": "plain run: the timed steps only; --full adds parity against the "
+                                           "fixtures, per-kernel times, the roofline and every other leg"}})
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            COMM.close()
+        return
 
     # ---- parity of the timed output, block by block, against the oracle's answers ----
     golden = golden_full
@@ -768,21 +852,8 @@ def main():
 
     if rank == 0:
         hot = {kk: round(v["ms"] / ks, 3) for kk, v in sorted(ktimes.items(), key=lambda kv: -kv[1]["ms"])[:14]}
-        out = {
-            "metric": "compress MB/s at fixed block size, bit-exact vs reference; 1/2/4/8-GPU scaling",
-            "value": round(value, 2), "unit": "MB/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(ms_step, 2), "higher_is_better": True, "scaling": "strong" if a.strong else "weak",
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": ("BASELINE config 4: enwik-style synthetic text (kolm.datagen.enwik_like, seed "
-                                    f"20251212), {a.mib} MiB TOTAL in {a.bs >> 20} MiB blocks sharded round-robin "
-                                    f"over {world} GPU(s), resident in HBM, candidates 0..8 + MDL, payloads emitted "
-                                    "in HBM" + (", RCCL gather to rank 0" if world > 1 else "")) if a.strong else
-                                   ("enwik-style synthetic text (kolm.datagen.enwik_like, seed 20251212+rank), "
-                                    f"{a.mib} MiB per GPU resident in HBM, {a.bs >> 20} MiB fixed blocks, "
-                                    "candidates 0..8 + MDL, payloads emitted in HBM"
-                                    + (", RCCL gather to rank 0" if world > 1 else "")),
-                       "block_size": a.bs, "bytes_per_gpu": n, "blocks_per_gpu": nb,
-                       "parallelism": f"block-shard x{world}"},
+        out = headline()
+        out.update({
             "roofline": roof,
             "cpu_baseline": cpu,
             "detail": {"parity_blocks": f"{parity['ok']}/{parity['blocks']}"
@@ -815,7 +886,7 @@ def main():
                        "solo_kernels_ms": {kk: round(v["ms"], 3) for kk, v in
                                            sorted(solo["times"].items(), key=lambda kv: -kv[1]["ms"])[:14]}
                        if solo else None},
-        }
+        })
         if os.environ.get("KOLM_BENCH_ALLK"):  # A/B tooling (tools/kab.sh): every kernel
             out["detail"]["kernels_all_ms_per_step"] = {kk: round(v["ms"] / ks, 3) for kk, v in ktimes.items()}
         if cpu:

@@ -6,7 +6,7 @@ mkdir -p $OUT
 for i in $(seq 1 $R); do
   for L in $A $B; do
     tag=$(basename $L .so)_$i
-    KOLM_LIB=$L timeout -k 10 240 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --full-steps 0 --decode-steps 0 \
+    KOLM_LIB=$L timeout -k 10 240 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --full-steps 0 --decode-steps 0 \
       --cdc-steps 0 --v2-steps 0 --host-steps 0 --no-serial-pass > $OUT/$tag.json 2> $OUT/$tag.err || { tail -20 $OUT/$tag.err; exit 1; }
     python3 -c "
 import json;d=json.load(open('$OUT/$tag.json'));t=d['detail']

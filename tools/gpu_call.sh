@@ -4,8 +4,8 @@
 # STEPs, run in order, each under its own time limit, stopping at the first failure:
 #   tests            pytest -m gpu (whole suite)
 #   tests:EXPR       pytest -m gpu -k EXPR
-#   bench            bench.py --steps 20 --warmup 5 (the driver's headline run)
-#   quick            bench.py hot path only, 5 steps
+#   bench            bench.py --full --steps 20 --warmup 5 (the headline and every other leg)
+#   quick            bench.py --full with every leg off: hot path, parity, per-kernel times, 5 steps
 #   smoke            __graft_entry__.smoke()
 #   profile          tools/gpu_profile.sh OUT/prof (rocprofv3 stats overlapped + serialised + PMC)
 #   profile_full     the same on the ids 0..9 step (Re-Pair included)
@@ -15,7 +15,7 @@ OUT=${1:-gpurun_out/call}
 shift
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-QUICK="--steps 5 --warmup 2 --no-cpu-baseline --full-steps 0 --decode-steps 0 --cdc-steps 0 --v2-steps 0 --config-steps 0 --host-steps 0 --c4-steps 0 --no-serial-pass"
+QUICK="--full --steps 5 --warmup 2 --no-cpu-baseline --full-steps 0 --decode-steps 0 --cdc-steps 0 --v2-steps 0 --config-steps 0 --host-steps 0 --c4-steps 0 --no-serial-pass"
 summ() {
   python3 -c "
 import json,sys;d=json.load(open('$1'));t=d['detail']
@@ -37,7 +37,7 @@ for step in "$@"; do
         -k "$(echo "${step#tests:}" | sed 's/+/ or /g')" > "$OUT/gpu_tests_k.log" 2>&1 || { tail -40 "$OUT/gpu_tests_k.log"; exit 1; }
       tail -3 "$OUT/gpu_tests_k.log" ;;
     bench)
-      timeout -k 10 600 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+      timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
         || { tail -30 "$OUT/bench.err"; exit 1; }
       summ "$OUT/bench.json" ;;
     quick)
@@ -53,7 +53,7 @@ for step in "$@"; do
     run:*)
       # run:TAG:VAR=v+VAR2=w:bench args (spaces as commas) — bench.py with those settings
       IFS=: read -r _ tag envs args <<< "$step"
-      env $(echo "$envs" | tr '+' ' ') KOLM_BENCH_ALLK=1 timeout -k 10 300 python bench.py $(echo "$args" | tr ',' ' ') \
+      env $(echo "$envs" | tr '+' ' ') KOLM_BENCH_ALLK=1 timeout -k 10 300 python bench.py --full $(echo "$args" | tr ',' ' ') \
         > "$OUT/run_$tag.json" 2> "$OUT/run_$tag.err" || { tail -30 "$OUT/run_$tag.err"; exit 1; }
       python3 -c "
 import json;d=json.load(open('$OUT/run_$tag.json'));t=d['detail']
@@ -74,7 +74,7 @@ if c:
     profile)
       bash tools/gpu_profile.sh "$OUT/prof" || exit 1 ;;
     profile_full)
-      bash tools/gpu_profile.sh "$OUT/prof_full" "--mib 256 --steps 1 --warmup 1 --kt-steps 1 --no-serial-pass --no-cpu-baseline --full-steps 1 --decode-steps 0 --cdc-steps 0 --v2-steps 0 --config-steps 0 --host-steps 0 --c4-steps 0" stats || exit 1 ;;
+      bash tools/gpu_profile.sh "$OUT/prof_full" "--full --mib 256 --steps 1 --warmup 1 --kt-steps 1 --no-serial-pass --no-cpu-baseline --full-steps 1 --decode-steps 0 --cdc-steps 0 --v2-steps 0 --config-steps 0 --host-steps 0 --c4-steps 0" stats || exit 1 ;;
     probe:*)
       # probe:KIND — rocprofv3 kernel trace of tools/lz_probe.py KIND (4 batches, the last kernel-timed)
       kind=${step#probe:}

@@ -7,7 +7,7 @@ never combined with sys/runtime traces), e.g.:
     rocprofv3 --pmc WRITE_SIZE  -d OUT/write --output-format csv -- python3 bench.py ...
     rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d OUT/hit --output-format csv -- ...
 then:  python tools/pmc_traffic.py OUT [BATCHES] > profiles/pmc_summary.json
-BATCHES = encode batches the profiled command ran (bench.py --warmup 1 --steps 1 --kt-steps 1
+BATCHES = encode batches the profiled command ran (bench.py --full --warmup 1 --steps 1 --kt-steps 1
 --no-serial-pass with every leg off: 3); with it every kernel also gets "bytes_per_batch"
 (its summed HBM bytes / BATCHES), which bench.py adds up over the sort-stream kernels.
 

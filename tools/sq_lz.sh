@@ -5,7 +5,7 @@
 #   bash tools/sq_lz.sh OUT [KERNEL_REGEX] [extra bench args]
 OUT=${1:-gpurun_out/sq}
 RE=${2:-k_lz_local}
-ARGS="--mib 256 --steps 1 --warmup 0 --kt-steps 1 --no-serial-pass --no-cpu-baseline --full-steps 0 --decode-steps 0 \
+ARGS="--full --mib 256 --steps 1 --warmup 0 --kt-steps 1 --no-serial-pass --no-cpu-baseline --full-steps 0 --decode-steps 0 \
 --cdc-steps 0 --v2-steps 0 --config-steps 0 --host-steps 0 --c4-steps 0 $3"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
