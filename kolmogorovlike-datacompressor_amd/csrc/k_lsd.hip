@@ -4,6 +4,7 @@
 // ballot ranking), then group starts, ranks and the next round's segments (k_sort.hip).
 // No host synchronisation: a fixed sequence of launches on the sort stream.
 #include "kolm_internal.h"
+#include "alpha_code.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -699,28 +700,45 @@ __global__ __launch_bounds__(WG) void k_r0_rk(Geom geo, u32 nwin, const u32* PP,
 // bytes -> w = 6, C = 10 characters in the same 8 LSD passes that held 8 raw bytes; bit
 // planes: w = 1, C = 32 in 4 passes).  Fewer positions stay active after round 0
 // (text: 60 % instead of 79 %) and the doubling rounds start at h = C.
+// Batches whose widest alphabet needs more than 4 bits take their keys from per-block
+// order-preserving prefix codes instead (alpha_code.h, k_keypos_r0c: text ~14.5 characters in the
+// 64 bits, 27 % of the positions still tied; h = 8).
 // ---------------------------------------------------------------------------------
-constexpr u32 AL_PER = 65536;  // bytes per workgroup of k_alpha_present
+constexpr u32 AL_PER = 65536;  // bytes per workgroup of k_alpha_weights
 
-// pres[b * 8 + (c >> 5)] bit (c & 31): byte value c occurs in block b
-__global__ __launch_bounds__(WG) void k_alpha_present(Geom geo, const u8* text, u32 parts, u32* pres) {
+// pres[b * 8 + (c >> 5)] bit (c & 31): byte value c occurs in block b (exact: every byte).
+// wts[b * 256 + c] (optional) += the occurrences of c in a fixed sample of the block: every 16th
+// 16-byte chunk counted from the block's base, so a block's weights (and its prefix codes) depend
+// on its bytes alone, never on its place in a batch.
+__global__ __launch_bounds__(WG) void k_alpha_weights(Geom geo, const u8* text, u32 parts, u32* pres, u32* wts) {
     __shared__ u32 f[256];
+    __shared__ u32 cn[256];
     f[threadIdx.x] = 0;
+    cn[threadIdx.x] = 0;
     __syncthreads();
     const u32 b = blockIdx.x / parts, part = blockIdx.x - b * parts;
-    const u32 lo = geo.base(b) + part * AL_PER, hi = min(lo + AL_PER, geo.end(b));
-    for (u32 i = lo + threadIdx.x; i < hi; i += WG) f[text[i]] = 1u;  // benign same-value races
+    const u32 base = geo.base(b), lo = base + part * AL_PER, hi = min(lo + AL_PER, geo.end(b));
+    for (u32 i = lo + threadIdx.x; i < hi; i += WG) {
+        const u32 c = text[i];
+        f[c] = 1u;  // benign same-value races
+        if (wts && ((i - base) & 0xF0u) == 0) atomicAdd(&cn[c], 1u);
+    }
     __syncthreads();
     const u64 m = __ballot(f[threadIdx.x] != 0);
     if ((threadIdx.x & 31) == 0) {
         const u32 word = (u32)(m >> (threadIdx.x & 32));
         if (word) atomicOr(&pres[(u64)b * 8 + (threadIdx.x >> 5)], word);
     }
+    if (wts && cn[threadIdx.x]) atomicAdd(&wts[(u64)b * 256 + threadIdx.x], cn[threadIdx.x]);
 }
 
-// code[b * 256 + c] = rank of byte c among block b's byte values; wmax = max bits per code
-__global__ __launch_bounds__(WG) void k_alpha_codes(const u32* pres, u8* code, u32* wmax) {
+// code[b * 256 + c] = rank of byte c among block b's byte values; wmax = max bits per code;
+// cw[b * 256 + c] (optional) = the block's order-preserving prefix code of c (alpha_code.h: one
+// node per thread, a barrier between the tree's levels)
+__global__ __launch_bounds__(WG) void k_alpha_codes(const u32* pres, const u32* wts, u8* code, u16* cw, u32* wmax) {
     __shared__ u32 pw[8];
+    __shared__ AcWork ak;
+    __shared__ u16 cws[256];
     const u32 b = blockIdx.x, c = threadIdx.x;
     if (c < 8) pw[c] = pres[(u64)b * 8 + c];
     __syncthreads();
@@ -728,11 +746,40 @@ __global__ __launch_bounds__(WG) void k_alpha_codes(const u32* pres, u8* code, u
     for (u32 k = 0; k < (c >> 5); ++k) r += __popc(pw[k]);
     r += __popc(pw[c >> 5] & ((1u << (c & 31)) - 1u));
     code[(u64)b * 256 + c] = (u8)r;
+    const bool here = (pw[c >> 5] >> (c & 31)) & 1u;
     if (c == 255) {
-        const u32 sigma = r + ((pw[7] >> 31) & 1u);
+        const u32 sigma = r + (here ? 1u : 0u);
         const u32 w = sigma > 1 ? 32 - __clz(sigma - 1) : 1u;
         atomicMax(wmax, w);
     }
+    if (!cw) return;
+    // ac_init in parallel: symbol c's slot is its rank r; the weights' running sums by one thread
+    // (256 additions)
+    cws[c] = 0;
+    for (u32 i = c; i < AC_NODES; i += WG) ak.lo[i] = ak.hi[i] = 0;
+    if (here) {
+        ak.sym[r] = (u8)c;
+        const u32 v = wts[(u64)b * 256 + c];
+        ak.cum[r + 1] = v ? v : 1u;
+    }
+    __syncthreads();
+    if (c == 255) {
+        const u32 sigma = r + (here ? 1u : 0u);
+        u64 acc = 0;
+        ak.cum[0] = 0;
+        for (u32 i = 1; i <= sigma; ++i) {
+            acc += ak.cum[i];
+            ak.cum[i] = acc;
+        }
+        ak.sigma = sigma;
+        ak.hi[1] = (u16)sigma;
+    }
+    __syncthreads();
+    for (u32 d = 0; d <= AC_MAXLEN; ++d) {
+        if (c < (1u << d)) ac_node(ak, (1u << d) + c, d, cws);
+        __syncthreads();
+    }
+    cw[(u64)b * 256 + c] = cws[c];
 }
 
 // Round-0 keys by position: KA = the low 32 bits, KB = the high bits of the packed codes of
@@ -847,6 +894,165 @@ __global__ __launch_bounds__(WG) void k_keypos_r0(LsdGeom g, const u8* code, u32
     }
 }
 
+// Round-0 keys from the block's order-preserving prefix codes (alpha_code.h): the key of position
+// p is the 64 bits of its rotation's code stream, KB = the high word, KA = the low one.  The
+// codes are 2..8 bits, so a key holds at least AC_R0_CHARS = 8 whole characters (text: ~14.5) and
+// reads at most AC_MAXREAD = 32.
+// Why any such key is valid, and the doubling rounds may start at h = 8 whatever the codes are:
+// the code is prefix-free and order-preserving, so two rotations' code streams compare like the
+// rotations themselves, and so do their first 64 bits unless those are equal; positions with
+// equal keys agree on every whole code inside the 64 bits, at least 8 characters.  So (1) the
+// groups are equal on at least h = 8 characters and (2) the order of the groups is a coarsening
+// of the true order.  With (1) and (2), sorting a group by group(p + h) is consistent: p, q of one
+// group agree on h characters, and group(p + h) < group(q + h) implies rotation(p + h) <
+// rotation(q + h) by (2); positions still tied then agree on 2 h characters, and (2) holds for
+// the refined groups.  "No group split in a round" still means p ~ q => p + k h ~ q + k h for
+// all k: the rotations are identical.
+// A workgroup owns one LSD tile: text [lo, hi + 32) and the block's code words in LDS; every
+// thread sums the code lengths of its 16 positions, the workgroup scans the 256 sums, the threads
+// write the tile's bit stream (most significant bit first) into LDS, and every position reads
+// three dwords at its bit offset and funnel-shifts.  Positions whose key may run past their
+// Lyndon factor's end (FEd < 33, conservatively: 32 characters is the most a key reads) are
+// rebuilt from the factor record (ac_key_wrap).  hist0 / sp: the first LSD pass's tile digit
+// counts, as in k_keypos_r0.
+constexpr u32 R0C_TAIL = AC_MAXREAD;                             // characters staged past the tile
+constexpr u32 R0C_WORDS = (LSD_T + R0C_TAIL) * AC_MAXLEN / 32 + 4;  // the tile's bit stream + 2 words read past an offset
+__global__ __launch_bounds__(WG) void k_keypos_r0c(LsdGeom g, const u16* cwt, u32* KA, u32* KB, u32* hist0,
+                                                   ScanParts sp) {
+    __shared__ __align__(16) u8 tx[LSD_T + 64];
+    __shared__ u16 cw[256];
+    __shared__ u32 bs[R0C_WORDS];
+    __shared__ u32 wsum[WG / 64];
+    __shared__ TileCounts h0;
+    u32 lo, hi, b;
+    const u32 tile = xcd_tile(), tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!g.range(tile, lo, hi, b)) {  // a tile past its block's end (the whole workgroup)
+        hist0[(u64)tile * 256 + tid] = 0;
+        return;
+    }
+    h0.clear();
+    const u32 N = (u32)g.geo.N;
+    cw[tid] = cwt[(u64)b * 256 + tid];
+    for (u32 i = tid; i < R0C_WORDS; i += WG) bs[i] = 0;
+    const u32 n = min(hi + R0C_TAIL, N) - lo;  // characters staged: n <= LSD_T + 32
+    if ((((uintptr_t)g.text + lo) & 3) == 0) {  // dword copies (a dword that starts before N is allocated)
+        const u32* src = reinterpret_cast<const u32*>(g.text + lo);
+        u32* dst = reinterpret_cast<u32*>(tx);
+        for (u32 i = tid; i < (n + 3) / 4; i += WG) dst[i] = src[i];
+    } else {
+        for (u32 i = tid; i < n; i += WG) tx[i] = g.text[lo + i];
+    }
+    __syncthreads();
+    const u32 i0 = tid * LSD_PT;
+    // bits of the thread's 16 characters, then of the tail's (one character per lane of wave 0)
+    u32 mine = 0;
+#pragma unroll
+    for (u32 e = 0; e < LSD_PT; ++e) mine += i0 + e < n ? ac_len(cw[tx[i0 + e]]) : 0u;
+    const u32 incl = wave_incl_scan(mine, OpAddU(), 0u);
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    u32 off = incl - mine, total = 0;
+#pragma unroll
+    for (u32 q = 0; q < WG / 64; ++q) {
+        off += q < wv ? wsum[q] : 0u;
+        total += wsum[q];
+    }
+    {
+        // the stream: codes appended at their bit offsets, whole dwords by atomic OR (the first
+        // and last dword of a thread's run are shared with its neighbours)
+        u32 o = off, wi = o >> 5, cur = 0;
+#pragma unroll
+        for (u32 e = 0; e < LSD_PT; ++e) {
+            const u16 v = i0 + e < n ? cw[tx[i0 + e]] : (u16)0;
+            const u32 l = ac_len(v), c = ac_bits(v), s = o & 31;
+            if (l) {
+                if (s + l < 32) {
+                    cur |= c << (32 - s - l);
+                } else {
+                    const u32 r = s + l - 32;  // bits that spill into the next dword (0: exactly full)
+                    atomicOr(&bs[wi], cur | (c >> r));
+                    ++wi;
+                    cur = r ? c << (32 - r) : 0u;
+                }
+                o += l;
+            }
+        }
+        if (cur) atomicOr(&bs[wi], cur);
+    }
+    if (wv == 0) {
+        const u32 x = LSD_T + lane;
+        const u16 v = lane < R0C_TAIL && x < n ? cw[tx[x]] : (u16)0;
+        const u32 l = ac_len(v), c = ac_bits(v);
+        const u32 o = total + wave_incl_scan(l, OpAddU(), 0u) - l, s = o & 31;
+        if (l) {
+            if (s + l <= 32) {
+                atomicOr(&bs[o >> 5], c << (32 - s - l));
+            } else {
+                const u32 r = s + l - 32;
+                atomicOr(&bs[o >> 5], c >> r);
+                atomicOr(&bs[(o >> 5) + 1], c << (32 - r));
+            }
+        }
+    }
+    __syncthreads();
+    if (lo + i0 < hi) {  // (no return: every thread reaches the histogram's barrier)
+        u8 fed[LSD_PT];
+        if (((lo + i0) & 15) == 0 && lo + i0 + LSD_PT <= hi) {
+#pragma unroll
+            for (u32 q = 0; q < LSD_PT / 16; ++q) {
+                const uint4 v = reinterpret_cast<const uint4*>(g.FEd + lo + i0)[q];
+                const u32 wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (u32 e = 0; e < 16; ++e) fed[16 * q + e] = (u8)(wd[e >> 2] >> (8 * (e & 3)));
+            }
+        } else {
+#pragma unroll
+            for (u32 e = 0; e < LSD_PT; ++e) fed[e] = lo + i0 + e < hi ? g.FEd[lo + i0 + e] : (u8)255;
+        }
+        u32 ka[LSD_PT], kb[LSD_PT];
+        u32 o = off;
+#pragma unroll
+        for (u32 e = 0; e < LSD_PT; ++e) {
+            const u32 wi = o >> 5, s = o & 31;
+            const u32 w0 = bs[wi], w1 = bs[wi + 1], w2 = bs[wi + 2];
+            kb[e] = __funnelshift_l(w1, w0, s);
+            ka[e] = __funnelshift_l(w2, w1, s);
+            o += i0 + e < n ? ac_len(cw[tx[i0 + e]]) : 0u;
+        }
+#pragma unroll
+        for (u32 e = 0; e < LSD_PT; ++e) {
+            const u32 p = lo + i0 + e;
+            if (p < hi && fed[e] <= AC_MAXREAD) {  // the key may wrap inside the factor
+                u32 fs, m;
+                g.fac.locate(g.geo, p, fs, m);
+                const u64 kk = ac_key_wrap(g.text + fs, m, p - fs, cw);
+                ka[e] = (u32)kk;
+                kb[e] = (u32)(kk >> 32);
+            }
+        }
+        const u32 p0 = lo + i0;
+        if ((p0 & 3) == 0 && p0 + LSD_PT <= hi) {
+#pragma unroll
+            for (u32 q = 0; q < LSD_PT / 4; ++q) {
+                reinterpret_cast<uint4*>(KA + p0)[q] = make_uint4(ka[4 * q], ka[4 * q + 1], ka[4 * q + 2], ka[4 * q + 3]);
+                reinterpret_cast<uint4*>(KB + p0)[q] = make_uint4(kb[4 * q], kb[4 * q + 1], kb[4 * q + 2], kb[4 * q + 3]);
+            }
+        } else {
+            for (u32 e = 0; e < LSD_PT && p0 + e < hi; ++e) {
+                KA[p0 + e] = ka[e];
+                KB[p0 + e] = kb[e];
+            }
+        }
+#pragma unroll
+        for (u32 e = 0; e < LSD_PT; ++e)
+            if (p0 + e < hi) h0.add(digit<0>(ka[e]));
+    }
+    __syncthreads();
+    const u32 v = h0.total(tid);
+    hist0[(u64)tile * 256 + tid] = v;
+    add_part_total(g, sp, tile, v);
+}
+
 template <int P, int SRC, int G, int OUT>
 void lsd_pass(const LsdGeom& g, u32 nt, const u32* kin, const u32* pin, u32* kout, u32* pout, const u32* kg,
               u32* hist, bool counted, hipStream_t s, KTimer* kt, const ScanParts& sp) {
@@ -939,31 +1145,44 @@ u32 launch_alpha(const Geom& geo, const u8* text, u32* pres, u8* code, u32* d_w,
         KOLM_HIP_CHECK(hipStreamSynchronize(s));
         return 8;
     }
-    launch_alpha_async(geo, text, pres, code, d_w, h_w, s, kt);
+    launch_alpha_async(geo, text, pres, code, nullptr, d_w, h_w, s, kt);
     KOLM_HIP_CHECK(hipStreamSynchronize(s));
     return alpha_width(*h_w);
 }
 
-void launch_alpha_async(const Geom& geo, const u8* text, u32* pres, u8* code, u32* d_w, u32* h_w, hipStream_t s,
-                        KTimer* kt, bool zeroed) {
+void launch_alpha_async(const Geom& geo, const u8* text, u32* pres, u8* code, u16* cw, u32* d_w, u32* h_w,
+                        hipStream_t s, KTimer* kt, bool zeroed) {
     if (!geo.N) {
         if (h_w) *h_w = 8;
         return;
     }
     const u32 parts = (geo.bs + AL_PER - 1) / AL_PER;
     if (!zeroed) {  // (zeroed: the caller's k_zero_spans cleared pres and *d_w)
-        KOLM_HIP_CHECK(hipMemsetAsync(pres, 0, sizeof(u32) * 8 * geo.nb, s));
+        KOLM_HIP_CHECK(hipMemsetAsync(pres, 0, sizeof(u32) * alpha_pres_words(geo.nb, cw != nullptr), s));
         KOLM_HIP_CHECK(hipMemsetAsync(d_w, 0, sizeof(u32), s));
     }
     {
-        KScope k(kt, KT_LSD, "k_alpha_present", geo.N);
-        k_alpha_present<<<parts * geo.nb, WG, 0, s>>>(geo, text, parts, pres);
-        k_alpha_codes<<<geo.nb, WG, 0, s>>>(pres, code, d_w);
+        // cw: the sampled symbol weights follow the presence bits in pres
+        u32* wts = cw ? pres + (u64)8 * geo.nb : nullptr;
+        KScope k(kt, KT_LSD, "k_alpha_weights", geo.N);
+        k_alpha_weights<<<parts * geo.nb, WG, 0, s>>>(geo, text, parts, pres, wts);
+        k_alpha_codes<<<geo.nb, WG, 0, s>>>(pres, wts, code, cw, d_w);
     }
     if (h_w) KOLM_HIP_CHECK(hipMemcpyAsync(h_w, d_w, sizeof(u32), hipMemcpyDeviceToHost, s));
 }
 
 u32 alpha_width(u32 h_w) { return std::max<u32>(1, std::min<u32>(8, h_w)); }
+
+u64 alpha_pres_words(u32 nb, bool weights) { return (u64)nb * (weights ? 8 + 256 : 8); }
+
+// Prefix-code keys when the batch's widest alphabet needs more than 4 bits: at w <= 4 the fixed
+// codes already pack 16 or more characters into a key (bit planes, two-symbol data).
+// KOLM_R0_CODE = 0 / 1 forces a form (read per call: tests and A/B runs).
+bool r0_code_mode(u32 w) {
+    if (getenv("KOLM_R0_CODE")) return atoi(getenv("KOLM_R0_CODE")) != 0;
+    return w > 4;
+}
+u32 r0_code_chars() { return AC_R0_CHARS; }
 
 // Round 0 of the cyclic sort: a stable sort of every block's positions by the packed codes
 // of their first C rotation characters (k_keypos_r0: KA = low 32 bits -> RK, KB = high bits
@@ -1005,9 +1224,12 @@ void launch_round0(const Geom& geo, const R0Bufs& t, Seg* next, u32* next_cnt, u
         auto spp = [&]() -> const ScanParts& { return sp[parts ? (pidx & 1) : 0]; };
         {
             // text + FEd 2 (+ factor starts near factor ends), KA 4 (+ KB 4)
-            KScope k(kt, KT_KEYGEN, "k_keypos_r0", N * (pb ? 10 : 6));
-            k_keypos_r0<<<nt, WG, 0, s>>>(g, t.code, t.chars, t.w, sh, t.RK, pb ? t.KP : nullptr, t.hist, spp(),
-                                          part);
+            KScope k(kt, KT_KEYGEN, t.cw ? "k_keypos_r0c" : "k_keypos_r0", N * (pb ? 10 : 6));
+            if (t.cw)  // prefix codes: 64 key bits (chars = 8, w = 8: D = 8, no padding, no partial character)
+                k_keypos_r0c<<<nt, WG, 0, s>>>(g, t.cw, t.RK, t.KP, t.hist, spp());
+            else
+                k_keypos_r0<<<nt, WG, 0, s>>>(g, t.code, t.chars, t.w, sh, t.RK, pb ? t.KP : nullptr, t.hist, spp(),
+                                              part);
         }
         // the first half's passes 2 -> 3 exchange one packed word per element (digit 3 and the
         // position inside the block) when a block position fits 24 bits

@@ -516,8 +516,9 @@ SortOut sort_pass(kolm_ctx* c, const Geom& geo, const u8* text, bool cyclic, Fac
             }
             if (round == 0 && cyclic && !alpha_ready) {
                 // the alphabet pass's presence bits (its width word cnt[C_ALPHA] is in span 1)
-                z.p[4] = c->get<u32>("r0pres", (u64)geo.nb * 8);
-                z.n[4] = (u32)geo.nb * 8;
+                // and the sampled symbol weights behind them
+                z.p[4] = c->get<u32>("r0pres", alpha_pres_words(geo.nb, true));
+                z.n[4] = (u32)alpha_pres_words(geo.nb, true);
             }
             if (zero_bins) {
                 z.p[4] = c->get<u32>("cls_bins", NCLASS * CLS_NBIN);
@@ -532,6 +533,7 @@ SortOut sort_pass(kolm_ctx* c, const Geom& geo, const u8* text, bool cyclic, Fac
             // characters (alphabet-compacted codes), no host round trips but one
             const u64 nt = lsd_tiles(geo) + 1;
             u8* code = c->get<u8>("r0code", (u64)geo.nb * 256);
+            u16* cw = c->get<u16>("r0cw", (u64)geo.nb * 256);
             u32 w;
             if (alpha_ready) {
                 KOLM_HIP_CHECK(hipStreamWaitEvent(s, alpha_ready, 0));
@@ -539,12 +541,17 @@ SortOut sort_pass(kolm_ctx* c, const Geom& geo, const u8* text, bool cyclic, Fac
                 w = alpha_width(h[H_ALPHA]);
             } else {
                 // the width back through the counter flag (no fills, no blit, no blocking sync)
-                launch_alpha_async(geo, text, c->get<u32>("r0pres", (u64)geo.nb * 8), code, cnt + C_ALPHA, nullptr,
-                                   s, c->kt(), true);
+                launch_alpha_async(geo, text, c->get<u32>("r0pres", alpha_pres_words(geo.nb, true)), code, cw,
+                                   cnt + C_ALPHA, nullptr, s, c->kt(), true);
                 c->read_counts(h + C_ALPHA, cnt + C_ALPHA, 1, s);
                 w = alpha_width(h[C_ALPHA]);
             }
-            const u32 C = std::max<u32>(1, std::min<u32>(32, 64 / w));
+            // keys from the blocks' order-preserving prefix codes (64 bits, at least 8 whole
+            // characters: h0 = 8 whatever the codes are) unless the fixed-width codes already
+            // pack 16 or more characters (w <= 4)
+            const bool codes = r0_code_mode(w);
+            if (codes) w = 8;
+            const u32 C = codes ? r0_code_chars() : std::max<u32>(1, std::min<u32>(32, 64 / w));
             h0 = C;
             R0Bufs r{text, FEd, fac, code, C, w, c->get<u32>("KP", N), a.K2, a.SA, a.K22, a.SA2, a.RK,
                      c->get<u32>("r0hist", nt * 256), c->get<u32>("r0tmax", nt), c->get<u32>("r0tmin", nt),
@@ -552,8 +559,11 @@ SortOut sort_pass(kolm_ctx* c, const Geom& geo, const u8* text, bool cyclic, Fac
                      c->get<u32>("r0swc", (u64)2 * geo.nb * 16 * 256)};
             r.rec[0] = c->get<u64>("r0rec0", N);
             r.rec[1] = c->get<u64>("r0rec1", N);
+            r.cw = codes ? cw : nullptr;
             out.r0_chars = C;
-            if (dbg) fprintf(stderr, "[kolm] round 0: %u characters of %u bits\n", C, w);
+            if (dbg)
+                fprintf(stderr, "[kolm] round 0: %u characters of %u bits%s\n", C, w,
+                        codes ? " (prefix codes, 64 key bits)" : "");
             launch_round0(geo, r, nxt, L.next_cnt, a.blk_split, s, c->kt());
             out.active += N;
             out.rounds = 1;
@@ -1087,9 +1097,12 @@ int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
     // Round 0's alphabet (per-block code tables + the batch's code width, one host read) on the
     // side / index stream beside Lyndon instead of on the sort stream after it: the host reads the
     // width while Lyndon runs, and round 0 follows Lyndon without a round trip of its own
+    // (the pass reads the text: on the side stream it follows that stream's wait for the upload)
+    if (side) KOLM_HIP_CHECK(hipStreamWaitEvent(c->rp, ev[0], 0));
     if (nb < 64) {
         c->active = xs;
-        launch_alpha_async(geo, d_text, c->get<u32>("r0pres", (u64)nb * 8), c->get<u8>("r0code", (u64)nb * 256),
+        launch_alpha_async(geo, d_text, c->get<u32>("r0pres", alpha_pres_words(nb, true)),
+                           c->get<u8>("r0code", (u64)nb * 256), c->get<u16>("r0cw", (u64)nb * 256),
                            c->get<u32>("r0w", 1), c->h_cnt + H_ALPHA, xs, c->kt());
         KOLM_HIP_CHECK(hipEventRecord(c->eva, xs));
         P.alpha_ready = c->eva;
@@ -1098,7 +1111,6 @@ int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
     LzArgs z = P.lz_args();
     // (k_lz_tiles, the tile index of the parse's forms 1 / 2, runs right before the parse: placed
     // ahead of the prevc wait or first on the index stream it measured no better)
-    if (side) KOLM_HIP_CHECK(hipStreamWaitEvent(c->rp, ev[0], 0));
     c->active = xs;
     {
         EmitArgs ce{};

@@ -375,15 +375,21 @@ struct R0Bufs {
     u32* HF;   // [lsd_tiles * WG] group-head masks (LSD_T / WG slots per thread)
     u32* swc = nullptr;  // [2 * nb * 16 * 256] per-(block, part) digit totals of the LSD scans / sweep passes
     u64* rec[2] = {nullptr, nullptr};  // [N] each: the LSD passes' (key, position) records (record mode)
+    const u16* cw = nullptr;  // [nb * 256] per-block prefix codes (alpha_code.h): set = keys from them, chars = w = 8
 };
 // per-block code tables for round 0 (alphabet compaction), max code width of the batch
 u32 launch_alpha(const Geom& geo, const u8* text, u32* pres, u8* code, u32* d_w, u32* h_w, bool compact,
                  hipStream_t s, KTimer* kt = nullptr);
 // the same without the host wait: the width lands in *h_w (pinned) once stream s passes this point;
 // alpha_width() turns it into the width launch_alpha returns
-void launch_alpha_async(const Geom& geo, const u8* text, u32* pres, u8* code, u32* d_w, u32* h_w, hipStream_t s,
-                        KTimer* kt = nullptr, bool zeroed = false);
+// cw (optional, [nb * 256]): also the blocks' order-preserving prefix codes, from symbol weights
+// sampled into pres + 8 * nb (pres then holds alpha_pres_words(nb, true) words)
+void launch_alpha_async(const Geom& geo, const u8* text, u32* pres, u8* code, u16* cw, u32* d_w, u32* h_w,
+                        hipStream_t s, KTimer* kt = nullptr, bool zeroed = false);
 u32 alpha_width(u32 h_w);
+u64 alpha_pres_words(u32 nb, bool weights);
+bool r0_code_mode(u32 w);  // round-0 keys from the prefix codes for a batch of code width w (KOLM_R0_CODE)
+u32 r0_code_chars();       // whole characters such a key is guaranteed to hold: h0 of the doubling rounds
 void launch_round0(const Geom& geo, const R0Bufs& t, Seg* next, u32* next_cnt, u32* blk_split, hipStream_t s,
                    KTimer* kt = nullptr);
 
