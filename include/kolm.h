@@ -148,8 +148,12 @@ int kolm_cdc_boundaries(const uint8_t* data, uint64_t n, uint32_t min_size, uint
  * _select_decoders, PY:2194-2207): block i = payloads[payload_off[i], payload_off[i+1]),
  * method id methods[i], original length orig_lens[i]; the blocks are written back to back
  * into out (sum of orig_lens bytes, out_cap available).  Method ids outside
- * KOLM_DECODE_MASK return KOLM_EARG; so do malformed payloads (message names the block). */
-#define KOLM_DECODE_MASK 0x3FFu  /* every candidate id 0..9 (raw, xor, bbwt family 2..6, lz77, lfsr_pred, repair) */
+ * KOLM_DECODE_MASK return KOLM_EARG; so do malformed payloads (message names the block).
+ * v2_new (id 10, decode_new_pipeline PY:1578-1648): Rice parameters k = 0..15 are decoded,
+ * every value an encoder writes (PY:1489 tries 0..15).  PY's decoder accepts any k byte; here
+ * a block whose k list holds a byte above 15 is a malformed payload (decode it on the host).
+ * id-10 blocks of 2^28 bytes or more return KOLM_EARG. */
+#define KOLM_DECODE_MASK 0x7FFu  /* every candidate id 0..10 (raw, xor, bbwt family 2..6, lz77, lfsr_pred, repair, v2_new) */
 int kolm_decode_blocks(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
                        const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap);
 

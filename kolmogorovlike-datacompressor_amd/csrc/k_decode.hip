@@ -1139,6 +1139,11 @@ void launch_dec_bw(const BwArgs& a, hipStream_t s) {
     k_dec_mtf_summary<<<(nch + DRT - 1) / DRT, DRT, 0, s>>>(a, nch);
     k_dec_mtf_compose<<<a.d.nlist, 256, 0, s>>>(a);
     k_dec_mtf_replay<<<(nch + DRT - 1) / DRT, DRT, 0, s>>>(a, nch);
+    launch_bwi(a, s);
+}
+
+void launch_bwi(const BwArgs& a, hipStream_t s) {
+    if (!a.d.nlist) return;
     const u32 nl = a.d.nlist;
     const u32 mx = a.tpb * BWI_TILE;  // >= the longest block
     k_bwi_hist<<<dim3(a.tpb, nl), 256, 0, s>>>(a);

@@ -2297,6 +2297,10 @@ static int check_decode(const uint64_t* payload_off, const uint32_t* methods, co
             return KOLM_EARG;
         }
         if (payload_off[i + 1] < payload_off[i]) return KOLM_EARG;
+        if (methods[i] == KOLM_M_V2NEW && orig_lens[i] >= (1u << 28)) {  // 8 plane blocks index in 32 bits
+            set_err("v2_new blocks of 2^28 bytes or more are not decoded on the device");
+            return KOLM_EARG;
+        }
         total += orig_lens[i];
     }
     if (total >= (1ull << 31)) {
@@ -2350,8 +2354,50 @@ static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off
     KOLM_HIP_CHECK(hipMemcpyAsync(dob, obase.data(), sizeof(u32) * (nb + 1), hipMemcpyHostToDevice, s));
     KOLM_HIP_CHECK(hipMemcpyAsync(dlist, flat.data(), sizeof(u32) * nb, hipMemcpyHostToDevice, s));
     KOLM_HIP_CHECK(hipMemsetAsync(dst, 0, sizeof(u32) * nb, s));
+    // v2_new (id 10): every block takes 8 plane slots; the blocks decode in groups whose slots
+    // (each as long as the group's longest block) stay under V2D_GROUP_POS plane positions,
+    // one group after another on the stream.  A single block always forms a group.
+    struct V2Group {
+        u32 l0, l1, maxn, pos;  // list range, longest block, plane positions
+    };
+    std::vector<V2Group> v2g;
+    const std::vector<u32>& v2l = lists[KOLM_M_V2NEW];
+    for (u32 i = 0; i < v2l.size(); ++i) {
+        const u32 n = orig_lens[v2l[i]];
+        if (!v2g.empty()) {
+            V2Group& g = v2g.back();
+            const u64 cnt = g.l1 - g.l0 + 1, mx = std::max(g.maxn, n);
+            if (cnt <= V2D_GROUP_BLOCKS && 8 * cnt * mx <= V2D_GROUP_POS) {
+                g.l1 = i + 1;
+                g.maxn = (u32)mx;
+                continue;
+            }
+        }
+        v2g.push_back(V2Group{i, i + 1, n, 0});
+    }
+    std::vector<u32> v2pb;  // plane offsets of group gi at [8 * l0 + gi, 8 * l1 + gi]
+    u64 v2pos = 0, v2cnt = 0, v2th = 0, v2nd = 0, v2cp = 0;
+    for (V2Group& g : v2g) {
+        u32 o = 0;
+        for (u32 i = g.l0; i < g.l1; ++i)
+            for (u32 j = 0; j < 8; ++j) {
+                v2pb.push_back(o);
+                o += orig_lens[v2l[i]];
+            }
+        v2pb.push_back(o);
+        g.pos = o;
+        const u64 cnt = g.l1 - g.l0, mx = std::max(g.maxn, 1u);
+        u32 sh = 6;
+        while ((mx + (1ull << sh) - 1) >> sh > BWI_NODES) ++sh;
+        v2pos = std::max<u64>(v2pos, o);
+        v2cnt = std::max(v2cnt, cnt);
+        v2th = std::max(v2th, 8 * cnt * ((mx + BWI_TILE - 1) / BWI_TILE) * 256);
+        v2nd = std::max<u64>(v2nd, 5 * 8 * cnt * ((mx + (1ull << sh) - 1) >> sh));
+        v2cp = std::max(v2cp, 8 * cnt * ((mx + V2D_CHUNK - 1) / V2D_CHUNK));
+    }
     BwArgs a{};
     const u64 T = total + 16;
+    const u64 XT = std::max(T, v2pos + 16);  // the inverse BBWT scratch serves ids 2..6, then the id-10 groups
     if (!bwl.empty()) {
         u32* dmeth = c->get<u32>("dec_meth", nb);
         u32* dvb = c->get<u32>("dec_vbase", nb + 1);
@@ -2369,10 +2415,10 @@ static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off
         const u64 nch = (u64)bwl.size() * a.cpb;
         a.summ = c->get<u8>("dec_summ", nch * 256 + 16);
         a.states = c->get<u8>("dec_states", nch * 256 + 16);
-        a.X[0] = c->get<u32>("dec_x0", T);
-        a.X[3] = c->get<u32>("dec_x3", T);
-        a.X[4] = c->get<u32>("dec_x4", T);
-        a.so = c->get<u64>("dec_so", T);
+        a.X[0] = c->get<u32>("dec_x0", XT);
+        a.X[3] = c->get<u32>("dec_x3", XT);
+        a.X[4] = c->get<u32>("dec_x4", XT);
+        a.so = c->get<u64>("dec_so", XT);
         a.tpb = (maxn + BWI_TILE - 1) / BWI_TILE;
         a.th = c->get<u32>("dec_th", (u64)bwl.size() * a.tpb * 256 + 16);
         a.sshift = 6;
@@ -2413,6 +2459,30 @@ static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off
         rea = c->get<u64>("dec_rea", T);
         reb = c->get<u64>("dec_reb", T);
     }
+    V2dArgs v2{};
+    BwArgs v2bw{};
+    u32 *v2pbase = nullptr, *v2ident = nullptr, *v2info = nullptr;
+    std::vector<u32> ident;
+    if (!v2g.empty()) {
+        v2pbase = c->get<u32>("v2d_pbase", v2pb.size());
+        v2ident = c->get<u32>("v2d_ident", 8 * v2cnt);
+        ident.resize(8 * v2cnt);
+        for (size_t i = 0; i < ident.size(); ++i) ident[i] = (u32)i;
+        KOLM_HIP_CHECK(hipMemcpyAsync(v2pbase, v2pb.data(), sizeof(u32) * v2pb.size(), hipMemcpyHostToDevice, s));
+        KOLM_HIP_CHECK(hipMemcpyAsync(v2ident, ident.data(), sizeof(u32) * ident.size(), hipMemcpyHostToDevice, s));
+        v2.pstat = c->get<u32>("v2d_pstat", 8 * v2cnt);
+        v2info = c->get<u32>("v2d_info", V2D_INFO * v2l.size());  // whole list: read again after the groups
+        v2.L = c->get<u8>("v2d_l", v2pos + 16);
+        v2.U = c->get<u8>("v2d_u", v2pos + 16);
+        v2.cpar = c->get<u32>("v2d_cpar", v2cp + 16);
+        v2bw.bw = v2.L;
+        v2bw.X[0] = c->get<u32>("dec_x0", XT);
+        v2bw.X[3] = c->get<u32>("dec_x3", XT);
+        v2bw.X[4] = c->get<u32>("dec_x4", XT);
+        v2bw.so = c->get<u64>("dec_so", XT);
+        v2bw.th = c->get<u32>("v2d_th", v2th + 16);
+        v2bw.nd = c->get<u32>("v2d_nodes", v2nd + 16);
+    }
     auto args = [&](u32 m) { return DecArgs{dpay, dpoff, dob, dout, dst, dlist + lstart[m], lstart[m + 1] - lstart[m]}; };
     if (ms) KOLM_HIP_CHECK(hipEventRecord(c->ev[0], s));
     launch_dec_raw(args(KOLM_M_RAW), s);
@@ -2421,6 +2491,28 @@ static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off
     if (!lists[KOLM_M_LZ77].empty()) launch_dec_lz77(args(KOLM_M_LZ77), tpos, tval, ntok, mark, src, s);
     if (!bwl.empty()) launch_dec_bw(a, s);
     if (rvals) launch_dec_repair(args(KOLM_M_REPAIR), rvals, rnval, recnt, rlen, rea, reb, s);
+    for (size_t gi = 0; gi < v2g.size(); ++gi) {
+        const V2Group& g = v2g[gi];
+        const u32 cnt = g.l1 - g.l0, mx = std::max(g.maxn, 1u);
+        v2.d = DecArgs{dpay, dpoff, dob, dout, dst, dlist + lstart[KOLM_M_V2NEW] + g.l0, cnt};
+        v2.pbase = v2pbase + 8 * (u64)g.l0 + gi;
+        v2.info = v2info + (u64)V2D_INFO * g.l0;
+        v2.tpc = (mx + V2D_CHUNK - 1) / V2D_CHUNK;
+        v2bw.d = DecArgs{nullptr, nullptr, v2.pbase, v2.U, v2.pstat, v2ident, 8 * cnt};
+        v2bw.tpb = (mx + BWI_TILE - 1) / BWI_TILE;
+        v2bw.sshift = 6;
+        while (((u64)mx + (1ull << v2bw.sshift) - 1) >> v2bw.sshift > BWI_NODES) ++v2bw.sshift;
+        v2bw.nnmax = (u32)(((u64)mx + (1ull << v2bw.sshift) - 1) >> v2bw.sshift);
+        KOLM_HIP_CHECK(hipMemsetAsync(v2.L, 0, (u64)g.pos + 16, s));  // run-start marks
+        launch_dec_v2_parse(v2, s);
+        launch_bwi(v2bw, s);
+        launch_dec_v2_pack(v2, s);  // the mapped bytes, into the output range: U is free for the next group
+    }
+    if (!v2g.empty()) {  // the automaton inverse needs no group scratch: one launch over every id-10 block
+        v2.d = DecArgs{dpay, dpoff, dob, dout, dst, dlist + lstart[KOLM_M_V2NEW], (u32)v2l.size()};
+        v2.info = v2info;
+        launch_dec_v2_auto(v2, s);
+    }
     if (ms) KOLM_HIP_CHECK(hipEventRecord(c->ev[1], s));
     std::vector<u32> st(nb);
     KOLM_HIP_CHECK(hipMemcpyAsync(st.data(), dst, sizeof(u32) * nb, hipMemcpyDeviceToHost, s));

@@ -584,6 +584,36 @@ struct BwArgs {
 constexpr u32 BWI_TILE = 4096;    // counting-sort tile of the inverse BBWT
 constexpr u32 BWI_NODES = 16384;  // ruling-set nodes per block (LDS-resident in k_bwi_nodes)
 void launch_dec_bw(const BwArgs& a, hipStream_t s);
+// the inverse BBWT alone (the k_bwi_* kernels): bw -> d.out for every listed block with status
+// DEC_OK; uses d.list / d.obase / d.status / d.out, bw, X, so, th, nd, tpb, sshift, nnmax
+void launch_bwi(const BwArgs& a, hipStream_t s);
+
+// ---- k_v2dec.hip: v2_new (id 10) decode, decode_new_pipeline PY:1578-1648 ----
+constexpr u32 V2D_CHUNK = 4096;  // positions per mark-parity chunk
+// Scratch groups.  Layout: a block's 8 planes lie back to back, each of the block's own length
+// (pbase).  Budget rule: a block joins the current group while 8 * blocks * (longest block of the
+// group) <= V2D_GROUP_POS (this bounds the per-slot arrays th / nd / cpar, sized by the longest
+// block, as well as the ~22 B per plane position of the inverse BBWT: about 1.4 GiB), and while
+// the group has at most V2D_GROUP_BLOCKS blocks.  Groups run one after another.
+constexpr u64 V2D_GROUP_POS = 1ull << 26;
+constexpr u32 V2D_GROUP_BLOCKS = 4096;
+constexpr u32 V2D_INFO = 12;  // info words per block: mode, param, raw_mask, b1_mask, 8 raw plane offsets
+struct V2dArgs {
+    DecArgs d;         // list = the id-10 blocks of this group (k_v2d_auto: of the whole batch)
+    const u32* pbase;  // [8 * nlist + 1] plane blocks: plane j of list entry li is pb = 8 * li + j
+    u32* pstat;        // [8 * nlist] 0 = encoded plane to invert, else skipped (raw plane / failed block)
+    u32* info;         // [V2D_INFO * nlist] written by the parse, read by pack and automaton inverse
+    u8* L;             // [plane positions] run-start marks, then the planes' BBWT strings (0/1 bytes)
+    u8* U;             // [plane positions] the planes after the inverse BBWT
+    u32* cpar;         // [8 * nlist * tpc] mark parity per 4 KiB chunk
+    u32 tpc;           // chunks per plane slot
+};
+// header + plane parse + L of every encoded plane; then launch_bwi over the plane blocks
+// (BwArgs: obase = pbase, status = pstat, bw = L, out = U); then the pack into d.out.  The
+// automaton inverse (d and info only) runs once over all id-10 blocks after the groups.
+void launch_dec_v2_parse(const V2dArgs& a, hipStream_t s);
+void launch_dec_v2_pack(const V2dArgs& a, hipStream_t s);
+void launch_dec_v2_auto(const V2dArgs& a, hipStream_t s);
 
 }  // namespace kolm
 

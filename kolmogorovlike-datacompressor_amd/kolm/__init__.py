@@ -43,7 +43,7 @@ __all__ = [
     "compress_blocks_fixed", "compress_blocks_cdc", "cdc_fast_boundaries_strict", "decompress",
     "fixed_boundaries", "bbwt_forward", "mtf_encode",
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
-    "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
+    "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats",
 ]
 
@@ -187,6 +187,29 @@ def encode_new_pipeline(block: bytes) -> bytes:
     return _batched_single(bytes(block), 10)
 
 
+def decode_new_pipeline(payload: bytes, n: int) -> bytes:
+    """Inverse of encode_new_pipeline (decode_new_pipeline PY:1578-1648, the automaton inverse
+    PY:1056-1092) on the GPU (csrc/k_v2dec.hip): one kolm_decode_blocks call.  Rice parameters
+    up to 15 (all an encoder writes); kolm.decode.decode_new_pipeline is the host decoder."""
+    try:
+        return _lib.decode_blocks([bytes(payload)], [10], [n])
+    except _lib.KolmError as e:
+        raise ValueError(str(e)) from None
+
+
+_V2_DEVICE_MAX = 1 << 28  # kolm_decode_blocks refuses longer id-10 blocks (8 plane blocks index in 32 bits)
+
+
+def _v2_k_above_15(payload: bytes) -> bool:
+    """Header peek of an id-10 payload: does its k list hold a Rice parameter the device does
+    not decode (> 15; PY's decoder accepts any byte, no encoder writes one)?"""
+    if len(payload) < 3 or (payload[0] & 7) > 4 or len(payload) < 3 + (payload[0] & 7):
+        return False
+    pos = 1 + (payload[0] & 7)
+    nenc = 8 - bin(payload[pos]).count("1")
+    return any(k > 15 for k in payload[pos + 2:pos + 2 + nenc])
+
+
 def _v2_new(block: bytes):
     if not G_V2_NEW:
         raise NameError("v2_new raises in the reference (PY:1037-1043); never selected")
@@ -312,15 +335,19 @@ def compress_blocks_cdc(data: bytes, min_size: int = 4096, avg_size: int = 8192,
 
 def decompress(container: bytes, device: bool = True) -> bytes:
     """Inverse of compress_blocks_fixed / compress_blocks_cdc / the reference's containers
-    (PY:2451-2550).  The TOC is parsed on the host; every block (ids 0..9: raw, xor, the
-    BBWT family, lz77, lfsr_pred and Re-Pair — KOLM_DECODE_MASK) is decoded on the GPU in
-    one kolm_decode_blocks batch (decode side: SURVEY §8f-4).  Only an id outside the
-    device mask would fall to the host decoders of kolm/decode.py; `device=False` (not in
-    PY) decodes everything on the host."""
+    (PY:2451-2550).  The TOC is parsed on the host; every block (ids 0..10: raw, xor, the
+    BBWT family, lz77, lfsr_pred, Re-Pair and v2_new — KOLM_DECODE_MASK) is decoded on the GPU
+    in one kolm_decode_blocks batch (decode side: SURVEY §8f-4).  The host decoders of
+    kolm/decode.py take an id outside the device mask and an id-10 block whose header lists a
+    Rice parameter above 15 (PY decodes any k byte; the device decodes 0..15, all that an
+    encoder writes) or that is 2^28 bytes or longer (the device's id-10 limit); `device=False`
+    (not in PY) decodes everything on the host."""
     mode, size_field, total_len, mids, orig, payloads = read_container(container)
     parts: List[Optional[bytes]] = [None] * len(mids)
     if device:
-        sel = [i for i, m in enumerate(mids) if (_lib.KOLM_DECODE_MASK >> m) & 1]
+        sel = [i for i, m in enumerate(mids)
+               if (_lib.KOLM_DECODE_MASK >> m) & 1
+               and not (m == 10 and orig[i] and (orig[i] >= _V2_DEVICE_MAX or _v2_k_above_15(payloads[i])))]
         if sel:
             try:
                 dec = _lib.decode_blocks([payloads[i] for i in sel], [mids[i] for i in sel],

@@ -137,7 +137,7 @@ SIGNATURES = [
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
 KOLM_ERCCL = -4
-KOLM_DECODE_MASK = 0x3FF  # methods decoded on the device: every id 0..9 (kolm.h)
+KOLM_DECODE_MASK = 0x7FF  # methods decoded on the device: every id 0..10 (kolm.h)
 
 
 def decode_blocks(payloads, methods, orig_lens) -> bytes:
