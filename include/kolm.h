@@ -46,6 +46,8 @@ extern "C" {
 #define KOLM_ENOINIT (-5)  /* kolm_init not called */
 #define KOLM_EFORMAT (-6)  /* malformed container (message: PY's ValueError text) */
 #define KOLM_ERANGE (-7)   /* a container field overflows (PY: struct.error) */
+#define KOLM_EVERIFY (-8)  /* verify on: an encode entry point produced a payload that does not
+                              decode to its input (message names block, method, offset) */
 
 /* Candidate method ids (index into PY _select_encoders(), PY:2152-2165). */
 #define KOLM_M_RAW 0
@@ -275,6 +277,65 @@ int kolm_cdc_boundaries_device(kolm_ctx* ctx, const uint8_t* d_data, uint64_t n,
 int kolm_decode_blocks_device(kolm_ctx* ctx, const void* d_payloads, const uint64_t* payload_off,
                               const uint32_t* methods, const uint32_t* orig_lens, uint32_t nblocks,
                               void* d_out, uint64_t out_cap, double* ms);
+
+/* ---- verify: decode the payloads where they lie and compare with the input --------- */
+/* The KOLR container carries no checksum; this is the check that payloads decode back to
+ * their input, made on the device: the payloads are decoded (the decoders of
+ * kolm_decode_blocks) into scratch, k_verify_cmp compares the scratch with the original
+ * (both resident), and one word per block comes back. */
+#define KOLM_VERIFY_EQUAL 0xFFFFFFFFu     /* per-block word: the block decodes to its input */
+#define KOLM_VERIFY_REJECTED 0xFFFFFFFEu  /* per-block word: the decoder rejected the payload */
+#define KOLM_VR_NONE 0      /* kolm_verify_report.first_bad_reason */
+#define KOLM_VR_DIFFER 1    /* bytes differ: first_bad_offset = first differing byte of the block */
+#define KOLM_VR_REJECTED 2  /* the decoder rejected the payload */
+#define KOLM_VR_LENGTH 3    /* kolm_verify_container only: total_len differs from the data's length */
+typedef struct kolm_verify_report {
+    uint32_t blocks;            /* blocks checked */
+    uint32_t bad_blocks;        /* of which: differing or rejected */
+    uint32_t first_bad_block;   /* the lowest-numbered bad block, its method id, the offset of */
+    uint32_t first_bad_method;  /* its first differing byte (0 when rejected) and the reason */
+    uint32_t first_bad_offset;
+    uint32_t first_bad_reason;  /* KOLM_VR_* */
+    uint64_t bytes;             /* decoded bytes compared */
+    double ms_decode;           /* device time of the decode kernels (HIP events) */
+    double ms_compare;          /* device time of k_verify_cmp */
+} kolm_verify_report;
+/* Original d_data (block i = [h_bounds[i], h_bounds[i+1]), h_bounds[0] = 0, nblocks + 1 host
+ * entries; any alignment) and payloads d_payloads (block i = [payload_off[i],
+ * payload_off[i+1]), method methods[i]; host arrays) are both device-resident.  h_first_bad
+ * (optional, nblocks host words) receives per block the offset of its first differing byte,
+ * KOLM_VERIFY_EQUAL or KOLM_VERIFY_REJECTED; *rep (optional) the summary.  KOLM_OK whenever
+ * the check ran, whether or not blocks differ; argument errors as kolm_decode_blocks_device
+ * (method ids outside KOLM_DECODE_MASK: KOLM_EARG, the block named).  The blocks are checked
+ * in groups whose decoded bytes stay under min(2^31 - 1, $KOLM_VERIFY_BYTES (default 1 GiB,
+ * read per call)); a single block always forms a group: the decode scratch is bounded and
+ * inputs of 2 GiB and more can be checked. */
+int kolm_verify_blocks_device(kolm_ctx* ctx, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                              const void* d_payloads, const uint64_t* payload_off, const uint32_t* methods,
+                              uint32_t* h_first_bad, kolm_verify_report* rep);
+/* A whole container against the data it should hold (host buffers, default context): the
+ * TOC by kolm_toc_read (KOLM_EFORMAT as there); total_len != n is reported as KOLM_VR_LENGTH
+ * without decoding (first_bad untouched); otherwise payloads and data go up, the grouped check
+ * runs and only the per-block words come down: first_bad[0, cap) (optional; KOLM_ECAP when
+ * cap < the block count), *rep the summary. */
+int kolm_verify_container(const uint8_t* container, uint64_t cn, const uint8_t* data, uint64_t n,
+                          uint32_t* first_bad, uint32_t cap, kolm_verify_report* rep);
+/* Verify-after-encode (default off, or KOLM_VERIFY=1 at context creation): when enabled,
+ * kolm_encode_blocks, kolm_encode_blocks_device, kolm_encode_blocks_device_var,
+ * kolm_compress_fixed (every device batch) and kolm_encode_blocks_multi (its per-device
+ * contexts take the default context's setting) check every batch on the resident text and
+ * arena before they return, after the emission kernels and under the context lock the call
+ * holds.  A bad block makes the call return KOLM_EVERIFY (kolm_last_error names the block, the
+ * method and the offset or "decoder rejected the payload"); kolm_compress_fixed then hands
+ * out no container (*out_len = 0), the other entry points still fill their outputs.
+ * Disabled: no extra launch, allocation or synchronisation.  $KOLM_VERIFY_INJECT=<block>
+ * (test switch, read per call, verify on only) xors 0x80 into the first payload byte of that
+ * block in the device arena before the check. */
+int kolm_ctx_set_verify(kolm_ctx* ctx, int enable);
+int kolm_set_verify(int enable);  /* default context */
+/* The report accumulated over the batches of the last encode call of ctx (NULL: the default
+ * context) that ran with verify enabled. */
+int kolm_ctx_verify_report(kolm_ctx* ctx, kolm_verify_report* rep);
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (kolm_comm.cpp) ------------- */
 /* The only data exchange of the multi-GPU path: blocks are independent (PY:2350-2369), so

@@ -26,6 +26,7 @@
 
 #include "../../include/kolm.h"
 #include "kolm_internal.h"
+#include "verify_core.h"
 
 using namespace kolm;
 
@@ -133,6 +134,23 @@ enum : int {
 
 struct kolm_ctx;
 namespace {
+// Milliseconds between two recorded events the device has already passed.  A batch's results
+// reach the host through coherent host words (read_spans), which the host can see before the
+// runtime has retired the events of the same stream: on hipErrorNotReady wait for the runtime
+// (no device wait is left) and ask again.  The usual case costs nothing extra.
+float event_ms(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    hipError_t e = hipEventElapsedTime(&ms, a, b);
+    if (e == hipErrorNotReady) {
+        (void)hipGetLastError();
+        KOLM_HIP_CHECK(hipEventSynchronize(a));
+        KOLM_HIP_CHECK(hipEventSynchronize(b));
+        e = hipEventElapsedTime(&ms, a, b);
+    }
+    KOLM_HIP_CHECK(e);
+    return ms;
+}
+
 // Records a HIP event pair around the launches in its scope (timing enabled only).
 struct TScope {
     kolm_ctx* c;
@@ -152,6 +170,13 @@ struct kolm_ctx {
     hipStream_t active = nullptr;  // stream used by launches / TScope / sync()
     hipStream_t rp = nullptr;      // third stream: Re-Pair (candidate 9), one workgroup per block
     bool serial = false;           // every launch of a batch on one stream (kolm_ctx_set_serial; KOLM_SERIAL=1)
+    // verify-after-encode (kolm_ctx_set_verify; KOLM_VERIFY=1): every encode batch is decoded and
+    // compared with its text before the call returns; vrep accumulates over the batches of one
+    // call (vrep.blocks = blocks checked so far), vshard = the call's first block within a
+    // multi-device encode
+    bool verify = false;
+    kolm_verify_report vrep{};
+    u32 vshard = 0;
     // pinned host staging: an upload ring (input chunks) and the result buffer of
     // kolm_compress_fixed (container bytes, valid until the next call on this context)
     static constexpr int NSTAGE = 4;
@@ -249,21 +274,29 @@ struct kolm_ctx {
         pend.clear();
         evused = 0;
     }
-    void timing_collect(kolm_stats* st) {
-        for (auto& p : pend) {
-            float ms = 0;
-            KOLM_HIP_CHECK(hipEventElapsedTime(&ms, p.a, p.b));
+    void timing_add(const Pend& p, kolm_stats* st) {
+        const float ms = event_ms(p.a, p.b);
+        if (st) {
             st->kt[p.fam].ms += ms;
             st->kt[p.fam].launches += 1;
             st->kt[p.fam].bytes += p.bytes;
-            Acc& a = kacc[p.name];
-            a.fam = p.fam;
-            a.strm = p.strm;
-            a.ms += ms;
-            a.launches += 1;
-            a.bytes += p.bytes;
         }
+        Acc& a = kacc[p.name];
+        a.fam = p.fam;
+        a.strm = p.strm;
+        a.ms += ms;
+        a.launches += 1;
+        a.bytes += p.bytes;
+    }
+    void timing_collect(kolm_stats* st) {
+        for (auto& p : pend) timing_add(p, st);
         timing_reset();
+    }
+    // only the launches recorded since pend held p0 entries (the verify step, which runs after
+    // a batch's own collection or without one); st optional
+    void timing_collect_tail(size_t p0, kolm_stats* st) {
+        for (size_t i = p0; i < pend.size(); ++i) timing_add(pend[i], st);
+        pend.resize(p0);
     }
 
     void* raw(const char* name, size_t bytes) {
@@ -880,11 +913,7 @@ struct Pipeline {
     }
 };
 
-float ev_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    KOLM_HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-    return ms;
-}
+float ev_ms(hipEvent_t a, hipEvent_t b) { return event_ms(a, b); }
 
 int check_geom(u64 N, u32 bs) {
     if (N >= (1ull << 31)) {
@@ -974,6 +1003,11 @@ bool v2_stage(kolm_ctx* c, const Geom& geo, const u8* d_text, hipStream_t s, V2S
 // Full batch: sizes of candidates 0..10, MDL, emission into d_arena.  Fixed blocks of bs
 // bytes over [0, N), or (h_bounds != null) the nbv content-defined blocks
 // [h_bounds[i], h_bounds[i+1]) (PY:2213 compress_blocks_cdc).
+// verify-after-encode of one batch (defined with the decode side below)
+int verify_encoded(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nb, u8* d_arena,
+                   const u64* off, const u32* win, hipEvent_t emitted, kolm_stats* stats);
+void verify_message(const kolm_verify_report& r);  // kolm_last_error text of a failed verify
+
 int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
                  const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
                  kolm_stats* stats) {
@@ -1370,6 +1404,9 @@ int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
             }
         }
     }
+    // the methods and offsets are on the host, the text and the arena still resident: decode the
+    // arena where it lies and compare (every output above is filled either way)
+    if (c->verify) return verify_encoded(c, d_text, N, bs, h_bounds, nb, d_arena, off.data(), win.data(), ev[4], stats);
     return KOLM_OK;
 }
 
@@ -1412,6 +1449,7 @@ int ctx_create(int device, kolm_ctx** out) {
         KOLM_HIP_CHECK(hipStreamCreateWithFlags(&c->rp, hipStreamNonBlocking));
         c->active = c->stream;
         c->serial = getenv("KOLM_SERIAL") && atoi(getenv("KOLM_SERIAL")) != 0;
+        c->verify = getenv("KOLM_VERIFY") && atoi(getenv("KOLM_VERIFY")) != 0;
         for (auto& e : c->evj) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evr) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evg) KOLM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1430,6 +1468,13 @@ int ctx_create(int device, kolm_ctx** out) {
 kolm_ctx* need_default() {
     std::lock_guard<std::mutex> g(g_mu);
     return g_default;
+}
+
+// start of an encode call (context lock held): the verify report covers this call's batches
+void verify_begin(kolm_ctx* c, u32 first_block = 0) {
+    if (!c->verify) return;
+    c->vrep = kolm_verify_report{};
+    c->vshard = first_block;
 }
 
 // Upload n host bytes to the context's "text" buffer (+64 bytes of zero padding).
@@ -1693,6 +1738,7 @@ int kolm_encode_blocks_device(kolm_ctx* c, const uint8_t* d_data, uint64_t total
     return guarded([&] {
         std::lock_guard<std::mutex> g(c->mu);
         KOLM_HIP_CHECK(hipSetDevice(c->device));
+        verify_begin(c);
         return encode_batch(c, d_data, total, block_size, nullptr, 0, cand_mask & KOLM_FULL_MASK, force_method,
                             d_arena, arena_cap, h_sizes, h_method, h_off, stats);
     });
@@ -1739,9 +1785,10 @@ int kolm_encode_blocks(const uint8_t* data, const uint64_t* starts, const uint32
         const u64 dcap = (has_raw ? total : 9 * total) + 64 * (u64)nblocks + 256;
         u8* arena = c->get<u8>("arena", dcap);
         std::vector<u64> off(nblocks + 1);
+        verify_begin(c);
         int r = encode_batch(c, d, total, bs, fixed ? nullptr : hb.data(), nblocks, cand_mask & KOLM_FULL_MASK,
                              force_method, arena, dcap, sizes, method, off.data(), stats);
-        if (r) return r;
+        if (r && r != KOLM_EVERIFY) return r;  // a failed verify still hands out the payloads
         if (off[nblocks] > arena_cap) {
             set_err("payload_arena too small");
             return KOLM_ECAP;
@@ -1751,7 +1798,7 @@ int kolm_encode_blocks(const uint8_t* data, const uint64_t* starts, const uint32
             c->sync();
         }
         std::memcpy(payload_off, off.data(), sizeof(u64) * (nblocks + 1));
-        return KOLM_OK;
+        return r;
     });
 }
 
@@ -1780,6 +1827,7 @@ int kolm_compress_fixed(const uint8_t* data, uint64_t n, uint32_t block_size, ui
     return guarded([&] {
         std::lock_guard<std::mutex> g(c->mu);
         KOLM_HIP_CHECK(hipSetDevice(c->device));
+        verify_begin(c);
         std::vector<u32> method(nb), lens(nb);
         std::vector<u64> plen(nb);
         for (u64 b = 0; b < nb; ++b) lens[b] = (u32)std::min<u64>(block_size, n - b * block_size);
@@ -1904,6 +1952,10 @@ int kolm_compress_fixed(const uint8_t* data, uint64_t n, uint32_t block_size, ui
             kolm_stats st{};
             int r = encode_batch(c, dtext[i & 1], len, block_size, nullptr, 0, cand_mask & KOLM_FULL_MASK, nullptr,
                                  arena + pos, acap - pos, nullptr, method.data() + b0, o.data(), &st);
+            if (r == KOLM_EVERIFY) {  // no container for payloads that do not decode
+                *out = nullptr;
+                *out_len = 0;
+            }
             if (r) return r;
             if (hprof) fprintf(stderr, "[kolm] host: piece %llu encoded %.2f ms\n", (unsigned long long)i, hms());
             for (u64 j = 0; j < k; ++j) plen[b0 + j] = o[j + 1] - o[j];
@@ -2016,9 +2068,20 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
     for (u32 r = 0; r <= G; ++r) b0[r] = (u32)((u64)nb * r / G);
     // the shards' payloads stay in each device's arena until the reassembly below
     static const bool host_gather = getenv("KOLM_MULTI_GATHER") && !strcmp(getenv("KOLM_MULTI_GATHER"), "host");
+    // verify: the per-device contexts take the default context's setting for this call
+    bool verify = false;
+    {
+        std::lock_guard<std::mutex> g(g_mu);
+        if (g_default) {
+            std::lock_guard<std::mutex> gc(g_default->mu);
+            verify = g_default->verify;
+        }
+    }
     struct Part {
         int rc = KOLM_OK;
         std::string err;
+        bool checked = false;  // verify ran on this shard
+        kolm_verify_report vrep{};
         const u8* d_pay = nullptr;
         std::vector<u64> off;
         kolm_stats st{};
@@ -2053,11 +2116,15 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
             const u64 dcap = (has_raw ? n : 9 * n) + 64 * (u64)nbr + 256;
             u8* arena = c->get<u8>("arena", dcap);
             P.off.assign(nbr + 1, 0);
+            c->verify = verify;
+            verify_begin(c, b0[r]);
             int rc = encode_batch(c, d, n, block_size, nullptr, 0, cand_mask & KOLM_FULL_MASK,
                                   force_method ? force_method + b0[r] : nullptr, arena, dcap,
                                   sizes ? sizes + (u64)b0[r] * KOLM_NCAND : nullptr, method ? method + b0[r] : nullptr,
                                   P.off.data(), stats ? &P.st : nullptr);
-            if (rc) return rc;
+            P.checked = verify;
+            P.vrep = c->vrep;
+            if (rc && rc != KOLM_EVERIFY) return rc;  // a failed verify still hands out the payloads
             P.d_pay = arena;
             return KOLM_OK;
         });
@@ -2150,6 +2217,36 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
             }
         }
         *stats = agg;
+    }
+    if (verify) {
+        // the shards' reports (block numbers are the call's) in shard order, kept on the default context
+        kolm_verify_report all{};
+        for (u32 r = 0; r < G; ++r) {
+            const kolm_verify_report& v = part[r].vrep;
+            if (!part[r].checked) continue;
+            if (all.bad_blocks == 0 && v.bad_blocks) {
+                all.first_bad_block = v.first_bad_block;
+                all.first_bad_method = v.first_bad_method;
+                all.first_bad_offset = v.first_bad_offset;
+                all.first_bad_reason = v.first_bad_reason;
+            }
+            all.blocks += v.blocks;
+            all.bad_blocks += v.bad_blocks;
+            all.bytes += v.bytes;
+            all.ms_decode = std::max(all.ms_decode, v.ms_decode);
+            all.ms_compare = std::max(all.ms_compare, v.ms_compare);
+        }
+        {
+            std::lock_guard<std::mutex> g(g_mu);
+            if (g_default) {
+                std::lock_guard<std::mutex> gc(g_default->mu);
+                g_default->vrep = all;
+            }
+        }
+        if (all.bad_blocks) {
+            verify_message(all);
+            return KOLM_EVERIFY;
+        }
     }
     return KOLM_OK;
 }
@@ -2275,6 +2372,7 @@ int kolm_encode_blocks_device_var(kolm_ctx* c, const uint8_t* d_data, const uint
     return guarded([&] {
         std::lock_guard<std::mutex> g(c->mu);
         KOLM_HIP_CHECK(hipSetDevice(c->device));
+        verify_begin(c);
         if (nblocks == 0) {
             if (h_off) h_off[0] = 0;
             if (stats) *stats = kolm_stats{};
@@ -2317,8 +2415,12 @@ static int check_decode(const uint64_t* payload_off, const uint32_t* methods, co
 // Decodes nb blocks whose payloads are resident at dpay (+ payload_off[i] - payload_off[0])
 // into dout (device).  Per-decoder block lists are built on the host; every kernel
 // runs on the context stream.  ms (optional) = device time of the decode kernels.
+// status_out (optional, the verify path): receives every block's DEC_* word instead of the call
+// failing at the first rejected block; d_obase then receives the device copy of the nb + 1
+// output offsets (valid until the next decode on the context).
 static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off, const uint32_t* methods,
-                        const uint32_t* orig_lens, u32 nb, u64 total, u8* dout, double* ms) {
+                        const uint32_t* orig_lens, u32 nb, u64 total, u8* dout, double* ms,
+                        std::vector<u32>* status_out = nullptr, const u32** d_obase = nullptr) {
     hipStream_t s = c->stream;
     std::vector<u64> poff(nb + 1);
     std::vector<u32> obase(nb + 1);
@@ -2522,6 +2624,11 @@ static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off
         KOLM_HIP_CHECK(hipEventElapsedTime(&f, c->ev[0], c->ev[1]));
         *ms = f;
     }
+    if (status_out) {
+        if (d_obase) *d_obase = dob;
+        status_out->swap(st);
+        return KOLM_OK;
+    }
     for (u32 i = 0; i < nb; ++i)
         if (st[i]) {
             char msg[128];
@@ -2571,6 +2678,227 @@ int kolm_decode_blocks_device(kolm_ctx* c, const void* d_payloads, const uint64_
         return decode_batch(c, static_cast<const u8*>(d_payloads) + payload_off[0], payload_off, methods, orig_lens,
                             nblocks, total, static_cast<u8*>(d_out), ms);
     });
+}
+
+}  // extern "C"
+
+// ---- verify: decode the payloads where they lie, compare with the original where it lies ----
+namespace {
+
+u64 verify_group_limit() {
+    u64 lim = 1ull << 30;
+    if (const char* e = getenv("KOLM_VERIFY_BYTES")) lim = std::max<u64>(1, strtoull(e, nullptr, 10));
+    return std::min<u64>(lim, (1ull << 31) - 1);
+}
+
+// Blocks [0, nb) of d_data (block i = [bounds[i], bounds[i + 1])) against their payloads at
+// d_pay + (poff[i] - poff[0]); both device-resident and complete as far as c->stream sees.
+// Groups of blocks whose decoded bytes stay under the limit (a single block always forms
+// one) are decoded into scratch placed congruent to the original mod 16, compared by
+// k_verify_cmp, and one word per block comes back: h_first_bad (optional) receives it, rep
+// accumulates (block numbers from block_base).  Context lock held, device set.
+int verify_run(kolm_ctx* c, const u8* d_data, const u64* bounds, u32 nb, const u8* d_pay, const u64* poff,
+               const u32* methods, u32* h_first_bad, u32 block_base, kolm_verify_report& rep, kolm_stats* stats) {
+    for (u32 i = 0; i < nb; ++i) {  // every argument check before the first launch
+        if (methods[i] >= 32 || !((KOLM_DECODE_MASK >> methods[i]) & 1u)) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "block %u: method %u is not decoded on the device", block_base + i, methods[i]);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        if (bounds[i + 1] < bounds[i] || poff[i + 1] < poff[i]) return KOLM_EARG;
+        if (bounds[i + 1] - bounds[i] >= (1ull << 31)) {
+            set_err("decoded batch larger than 2^31-1 bytes");
+            return KOLM_EARG;
+        }
+    }
+    const u64 lim = verify_group_limit();
+    hipStream_t s = c->stream;
+    c->active = s;
+    const size_t p0 = c->pend.size();
+    std::vector<u32> lens, st, fb;
+    for (u32 g0 = 0; g0 < nb;) {
+        u32 g1 = g0 + 1;
+        u64 tot = bounds[g1] - bounds[g0];
+        while (g1 < nb && tot + (bounds[g1 + 1] - bounds[g1]) <= lim) {
+            tot += bounds[g1 + 1] - bounds[g1];
+            ++g1;
+        }
+        const u32 n = g1 - g0;
+        lens.resize(n);
+        for (u32 i = 0; i < n; ++i) lens[i] = (u32)(bounds[g0 + i + 1] - bounds[g0 + i]);
+        u64 total = 0;
+        if (int rc = check_decode(poff + g0, methods + g0, lens.data(), n, tot, total)) return rc;
+        const u8* orig = d_data + bounds[g0];
+        u8* raw = c->get<u8>("vfy_dec", tot + 64 + 2 * vfy::WORD);
+        u8* dec = raw + ((reinterpret_cast<uintptr_t>(orig) - reinterpret_cast<uintptr_t>(raw)) & (vfy::WORD - 1));
+        u32* dfb = c->get<u32>("vfy_fb", n);
+        const u32* dob = nullptr;
+        double ms = 0.0;
+        if (int rc = decode_batch(c, d_pay + (poff[g0] - poff[0]), poff + g0, methods + g0, lens.data(), n, tot, dec, &ms,
+                                  &st, &dob))
+            return rc;
+        KOLM_HIP_CHECK(hipMemsetAsync(dfb, 0xFF, sizeof(u32) * n, s));
+        KOLM_HIP_CHECK(hipEventRecord(c->ev[2], s));
+        if (tot) {
+            TScope t(c, KOLM_KT_EMIT, "k_verify_cmp", 2 * tot);
+            launch_verify_cmp(dec, orig, (u32)tot, dob, n, dfb, s);
+        }
+        KOLM_HIP_CHECK(hipEventRecord(c->ev[3], s));
+        fb.resize(n);
+        KOLM_HIP_CHECK(hipMemcpyAsync(fb.data(), dfb, sizeof(u32) * n, hipMemcpyDeviceToHost, s));
+        c->sync();
+        rep.ms_decode += ms;
+        rep.ms_compare += ev_ms(c->ev[2], c->ev[3]);
+        for (u32 i = 0; i < n; ++i) {
+            // a rejected block is reported as rejected whatever the compare saw in its range:
+            // the scratch may hold an earlier decode of the same input
+            const u32 w = st[i] ? (u32)KOLM_VERIFY_REJECTED : fb[i];
+            if (h_first_bad) h_first_bad[g0 + i] = w;
+            if (w == KOLM_VERIFY_EQUAL) continue;
+            if (rep.bad_blocks++ == 0) {
+                rep.first_bad_block = block_base + g0 + i;
+                rep.first_bad_method = methods[g0 + i];
+                rep.first_bad_offset = st[i] ? 0u : w;
+                rep.first_bad_reason = st[i] ? KOLM_VR_REJECTED : KOLM_VR_DIFFER;
+            }
+        }
+        rep.blocks += n;
+        rep.bytes += tot;
+        g0 = g1;
+    }
+    if (c->timing) c->timing_collect_tail(p0, stats);
+    return KOLM_OK;
+}
+
+void verify_message(const kolm_verify_report& r) {
+    char msg[192];
+    if (r.first_bad_reason == KOLM_VR_REJECTED)
+        snprintf(msg, sizeof msg, "verify: block %u (method %u): decoder rejected the payload (%u bad of %u blocks)",
+                 r.first_bad_block, r.first_bad_method, r.bad_blocks, r.blocks);
+    else
+        snprintf(msg, sizeof msg,
+                 "verify: block %u (method %u): payload decodes to other bytes, first at offset %u (%u bad of %u blocks)",
+                 r.first_bad_block, r.first_bad_method, r.first_bad_offset, r.bad_blocks, r.blocks);
+    set_err(msg);
+}
+
+int verify_encoded(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nb, u8* d_arena,
+                   const u64* off, const u32* win, hipEvent_t emitted, kolm_stats* stats) {
+    std::vector<u64> bounds((size_t)nb + 1);
+    for (u32 i = 0; i <= nb; ++i) bounds[i] = h_bounds ? (u64)h_bounds[i] : std::min<u64>(N, (u64)i * bs);
+    // after the emission kernels, on the stream the decode runs on
+    KOLM_HIP_CHECK(hipStreamWaitEvent(c->stream, emitted, 0));
+    const u32 base = c->vshard + c->vrep.blocks;
+    if (const char* e = getenv("KOLM_VERIFY_INJECT")) {  // test switch: corrupt one payload byte
+        char* end = nullptr;
+        const u64 idx = strtoull(e, &end, 10);
+        if (end != e && idx >= base && idx < (u64)base + nb && off[idx - base + 1] > off[idx - base])
+            launch_verify_flip(d_arena + off[idx - base], c->stream);
+    }
+    const u32 bad0 = c->vrep.bad_blocks;
+    if (int rc = verify_run(c, d_text, bounds.data(), nb, d_arena, off, win, nullptr, base, c->vrep, stats)) return rc;
+    if (c->vrep.bad_blocks == bad0) return KOLM_OK;
+    verify_message(c->vrep);
+    return KOLM_EVERIFY;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kolm_ctx_set_verify(kolm_ctx* c, int enable) {
+    if (!c) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->verify = enable != 0;
+    return KOLM_OK;
+}
+
+int kolm_set_verify(int enable) {
+    kolm_ctx* c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    return kolm_ctx_set_verify(c, enable);
+}
+
+int kolm_ctx_verify_report(kolm_ctx* c, kolm_verify_report* rep) {
+    if (!c) c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    if (!rep) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    *rep = c->vrep;
+    return KOLM_OK;
+}
+
+int kolm_verify_blocks_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                              const void* d_payloads, const uint64_t* payload_off, const uint32_t* methods,
+                              uint32_t* h_first_bad, kolm_verify_report* rep) {
+    if (!c) return KOLM_EARG;
+    if (nblocks && (!d_data || !h_bounds || !d_payloads || !payload_off || !methods)) return KOLM_EARG;
+    kolm_verify_report r{};
+    if (rep) *rep = r;
+    if (nblocks == 0) return KOLM_OK;
+    if (h_bounds[0] != 0) return KOLM_EARG;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        return verify_run(c, static_cast<const u8*>(d_data), h_bounds, nblocks,
+                          static_cast<const u8*>(d_payloads) + payload_off[0], payload_off, methods, h_first_bad, 0, r,
+                          nullptr);
+    });
+    if (rep) *rep = r;
+    return rc;
+}
+
+int kolm_verify_container(const uint8_t* container, uint64_t cn, const uint8_t* data, uint64_t n,
+                          uint32_t* first_bad, uint32_t cap, kolm_verify_report* rep) {
+    kolm_ctx* c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    if ((!container && cn) || (!data && n)) return KOLM_EARG;
+    kolm_verify_report r{};
+    if (rep) *rep = r;
+    u32 fields[4] = {};
+    u64 start = 0;
+    std::vector<u32> methods(65536), lens(65536);
+    std::vector<u64> poff(65537);
+    if (int rc = kolm_toc_read(container, cn, fields, &start, methods.data(), lens.data(), poff.data(), 65536)) return rc;
+    const u32 nb = fields[3];
+    r.blocks = nb;
+    if (fields[2] != n) {
+        r.bad_blocks = nb;
+        r.first_bad_reason = KOLM_VR_LENGTH;
+        if (rep) *rep = r;
+        return KOLM_OK;
+    }
+    if (first_bad && cap < nb) {
+        set_err("first_bad capacity too small");
+        return KOLM_ECAP;
+    }
+    r.blocks = 0;
+    if (nb == 0) return KOLM_OK;
+    std::vector<u64> bounds((size_t)nb + 1, 0);
+    for (u32 i = 0; i < nb; ++i) bounds[i + 1] = bounds[i] + lens[i];
+    if (bounds[nb] != n) {  // the TOC's lengths do not add up to total_len
+        r.bad_blocks = nb;
+        r.blocks = nb;
+        r.first_bad_reason = KOLM_VR_LENGTH;
+        if (rep) *rep = r;
+        return KOLM_OK;
+    }
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        const u64 ptotal = poff[nb] - poff[0];
+        u8* dpay = c->get<u8>("vfy_pay", ptotal + 64);
+        u8* ddat = c->get<u8>("vfy_data", n + 64);
+        if (ptotal)
+            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, container + start + poff[0], ptotal, hipMemcpyHostToDevice, c->stream));
+        if (n) KOLM_HIP_CHECK(hipMemcpyAsync(ddat, data, n, hipMemcpyHostToDevice, c->stream));
+        return verify_run(c, ddat, bounds.data(), nb, dpay, poff.data(), methods.data(), first_bad, 0, r, nullptr);
+    });
+    if (rep) *rep = r;
+    return rc;
 }
 
 int kolm_bbwt_forward(const uint8_t* in, size_t n, uint8_t* out) {

@@ -615,6 +615,14 @@ void launch_dec_v2_parse(const V2dArgs& a, hipStream_t s);
 void launch_dec_v2_pack(const V2dArgs& a, hipStream_t s);
 void launch_dec_v2_auto(const V2dArgs& a, hipStream_t s);
 
+// ---- k_verify.hip: the decoded batch against the original (verify_core.h) ----
+// dec and orig: total (< 2^31) bytes each, addresses congruent mod 16; bounds [nb + 1] block
+// offsets (device); first_bad [nb], preset to 0xFFFFFFFF, ends as each block's first differing
+// offset.  Reads [0, total) of both buffers and nothing else.
+void launch_verify_cmp(const u8* dec, const u8* orig, u32 total, const u32* bounds, u32 nb, u32* first_bad,
+                       hipStream_t s);
+void launch_verify_flip(u8* p, hipStream_t s);  // *p ^= 0x80 (KOLM_VERIFY_INJECT)
+
 }  // namespace kolm
 
 #define KOLM_HIP_CHECK(x)                                              \

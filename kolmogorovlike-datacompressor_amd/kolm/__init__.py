@@ -34,8 +34,8 @@ import struct
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 from . import _lib
-from ._lib import KolmError, KolmUnavailable  # noqa: F401
-from .container import (MODE_CDC, MODE_FIXED, read_container, uleb128_decode_stream,  # noqa: F401
+from ._lib import KolmError, KolmUnavailable, KolmVerifyError  # noqa: F401
+from .container import (MODE_CDC, MODE_FIXED, read_container, read_toc, uleb128_decode_stream,  # noqa: F401
                         uleb128_encode, write_container)
 from .decode import decode_block
 
@@ -44,7 +44,7 @@ __all__ = [
     "fixed_boundaries", "bbwt_forward", "mtf_encode",
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
-    "KolmUnavailable", "KolmError", "last_stats",
+    "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
 ]
 
 CANDIDATE_NAMES = ["raw", "xor", "bbwt", "bbwt_bp", "bbwt_nib", "bbwt_br", "bbwt_gray", "lz77",
@@ -56,6 +56,9 @@ G_NO_LZ77: bool = False
 G_ONLY_METHOD: Optional[str] = None
 # candidate 10 (v2_new) with its automaton evaluated serially; PY as shipped raises instead
 G_V2_NEW: bool = False
+# verify-after-encode (not in PY): every encode batch is decoded on the device and compared
+# with its input before the call returns; a bad block raises KolmVerifyError
+G_VERIFY: bool = False
 
 _last_stats: Dict[str, Any] = {}
 
@@ -63,6 +66,16 @@ _last_stats: Dict[str, Any] = {}
 def last_stats() -> Dict[str, Any]:
     """Device statistics of the last batched call (rounds, active positions, ms per stage)."""
     return dict(_last_stats)
+
+
+def last_verify() -> Dict[str, Any]:
+    """Report of the last verified encode call (kolm_verify_report): blocks, bad_blocks,
+    first_bad_block / _method / _offset / _reason, bytes, ms_decode, ms_compare."""
+    return _lib.last_verify()
+
+
+def _want_verify(verify: Optional[bool]) -> bool:
+    return G_VERIFY if verify is None else bool(verify)
 
 
 # ---------------------------------------------------------------------------
@@ -271,9 +284,11 @@ def candidate_mask(hot_path: bool = False, v2_new: Optional[bool] = None) -> int
 # ---------------------------------------------------------------------------
 
 def encode_blocks(data: bytes, block_size: int, cand_mask: Optional[int] = None, devices: int = 1,
-                  hot_path: bool = False, v2_new: Optional[bool] = None):
+                  hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None):
     """Batched device MDL over fixed blocks: (method_ids, orig_lens, payloads, sizes).
-    devices > 1 shards the blocks over that many GPUs of this process."""
+    devices > 1 shards the blocks over that many GPUs of this process.  `verify` (default
+    G_VERIFY): the payloads are decoded and compared with the input on the device before the
+    call returns (KolmVerifyError otherwise)."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
     global _last_stats
@@ -282,20 +297,23 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: Optional[int] = None,
     if n == 0:
         return [], [], [], None
     if devices > 1:
-        sizes, method, payloads, st = _lib.encode_blocks_multi(bytes(data), block_size, devices, mask)
+        sizes, method, payloads, st = _lib.encode_blocks_multi(bytes(data), block_size, devices, mask,
+                                                               verify=_want_verify(verify))
     else:
-        sizes, method, payloads, st = _lib.encode_blocks(bytes(data), block_size, mask)
+        sizes, method, payloads, st = _lib.encode_blocks(bytes(data), block_size, mask, verify=_want_verify(verify))
     _last_stats = st
     orig = [min(block_size, n - i) for i in range(0, n, block_size)]
     return [int(m) for m in method], orig, payloads, sizes
 
 
 def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1, hot_path: bool = False,
-                          v2_new: Optional[bool] = None) -> bytes:
+                          v2_new: Optional[bool] = None, verify: Optional[bool] = None) -> bytes:
     """Fixed-size chunking + per-block MDL selection + KOLR container (PY:2332-2445).
     `devices` (not in PY) spreads the blocks over that many GPUs of this process;
     `hot_path` (not in PY) restricts the candidates to ids 0..8; `v2_new` (default
-    G_V2_NEW) adds candidate 10 (see the module docstring)."""
+    G_V2_NEW) adds candidate 10 (see the module docstring); `verify` (not in PY, default
+    G_VERIFY) checks on the device that every payload decodes to its block before the
+    container is handed out (KolmVerifyError, and no container, otherwise; last_verify())."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
     global _last_stats
@@ -304,22 +322,23 @@ def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1,
     if nb > 0xFFFF:
         raise struct.error("'H' format requires 0 <= number <= 65535")
     if devices > 1:
-        mids, orig, payloads, _ = encode_blocks(data, block_size, devices=devices, hot_path=hot_path, v2_new=v2_new)
+        mids, orig, payloads, _ = encode_blocks(data, block_size, devices=devices, hot_path=hot_path, v2_new=v2_new,
+                                                verify=verify)
         return write_container(MODE_FIXED, block_size, n, mids, orig, payloads)
     if n == 0:
         return write_container(MODE_FIXED, block_size, 0, [], [], [])
     # one native call: staged upload, batched encode, TOC, payloads into the container
-    blob, st = _lib.compress_fixed(data, block_size, candidate_mask(hot_path, v2_new))
+    blob, st = _lib.compress_fixed(data, block_size, candidate_mask(hot_path, v2_new), verify=_want_verify(verify))
     _last_stats = st
     return blob
 
 
 def compress_blocks_cdc(data: bytes, min_size: int = 4096, avg_size: int = 8192, max_size: int = 16384,
-                        hot_path: bool = False, v2_new: Optional[bool] = None) -> bytes:
+                        hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None) -> bytes:
     """FastCDC chunking + per-block MDL selection + KOLR container in CDC mode
     (PY:2213-2326): boundaries and every candidate on the GPU, one batched device call for
     all chunks (variable block geometry), the TOC on the host.  `hot_path` (not in PY)
-    restricts the candidates to ids 0..8."""
+    restricts the candidates to ids 0..8; `verify` as in compress_blocks_fixed."""
     global _last_stats
     bounds = cdc_fast_boundaries_strict(data, min_size, avg_size, max_size)
     if len(bounds) > 0xFFFF:  # PY packs the block count as '<H' before encoding (PY:2222)
@@ -328,7 +347,8 @@ def compress_blocks_cdc(data: bytes, min_size: int = 4096, avg_size: int = 8192,
     if n == 0:
         return write_container(MODE_CDC, avg_size, 0, [], [], [])
     edges = [s for s, _ in bounds] + [n]
-    _, method, payloads, st = _lib.encode_blocks_var(bytes(data), edges, candidate_mask(hot_path, v2_new))
+    _, method, payloads, st = _lib.encode_blocks_var(bytes(data), edges, candidate_mask(hot_path, v2_new),
+                                                     verify=_want_verify(verify))
     _last_stats = st
     return write_container(MODE_CDC, avg_size, n, [int(m) for m in method], [e - s for s, e in bounds], payloads)
 
@@ -364,3 +384,23 @@ def decompress(container: bytes, device: bool = True) -> bytes:
     if len(out) != total_len:
         raise ValueError(f"Length mismatch: got {len(out)}, expect {total_len}")
     return bytes(out)
+
+
+def verify(container: bytes, data: bytes) -> Dict[str, Any]:
+    """Does `container` hold `data`?  Checked on the device (kolm_verify_container): the
+    payloads and the data go up, every block is decoded and compared there, and one word per
+    block comes back.  Returns {"ok", "blocks", "bad": [(block, method, offset, reason), ...],
+    "reason", "bytes", "ms_decode", "ms_compare"}: reason 1 bytes differ (offset = the block's
+    first differing byte), 2 the decoder rejected the payload, 3 the container's total length
+    is not len(data) (nothing decoded, "bad" empty).  A malformed container raises the
+    ValueError decompress raises; every method id must be in KOLM_DECODE_MASK."""
+    fb, rep = _lib.verify_container(container, data)
+    bad: List[Tuple[int, int, int, int]] = []
+    if fb is not None and rep["bad_blocks"]:
+        _, _, _, mids, _, _, _ = read_toc(bytes(container))
+        for i in (int(j) for j in (fb != _lib.KOLM_VERIFY_EQUAL).nonzero()[0]):
+            rej = int(fb[i]) == _lib.KOLM_VERIFY_REJECTED
+            bad.append((i, int(mids[i]), 0 if rej else int(fb[i]), _lib.VR_REJECTED if rej else _lib.VR_DIFFER))
+    return {"ok": rep["bad_blocks"] == 0 and rep["first_bad_reason"] == _lib.VR_NONE, "blocks": rep["blocks"],
+            "bad": bad, "reason": rep["first_bad_reason"], "bytes": rep["bytes"],
+            "ms_decode": rep["ms_decode"], "ms_compare": rep["ms_compare"]}

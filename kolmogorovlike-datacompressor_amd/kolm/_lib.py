@@ -28,8 +28,13 @@ KOLM_HOTPATH_MASK = 0x1FF  # BBWT / MTF+Rice / LZ77 path, ids 0..8
 KOLM_REPAIR_MAX_BLOCK = 1 << 22
 KOLM_EFORMAT = -6
 KOLM_ERANGE = -7
+KOLM_EVERIFY = -8
 ERRORS = {-1: "bad argument", -2: "capacity too small", -3: "HIP error", -4: "collective error",
-          -5: "not initialised", -6: "malformed container", -7: "field overflow"}
+          -5: "not initialised", -6: "malformed container", -7: "field overflow",
+          -8: "payload does not decode to its input"}
+KOLM_VERIFY_EQUAL = 0xFFFFFFFF     # per-block word of the verify entry points: the block is equal
+KOLM_VERIFY_REJECTED = 0xFFFFFFFE  # the decoder rejected the payload
+VR_NONE, VR_DIFFER, VR_REJECTED, VR_LENGTH = 0, 1, 2, 3  # kolm_verify_report.first_bad_reason
 
 
 class KolmUnavailable(ImportError):
@@ -44,6 +49,21 @@ class KolmError(RuntimeError):
 
 KT_NAMES = ["classify", "keygen", "msd", "small_sort", "lsd", "lz_parse", "mtf", "sizes", "emit",
             "lyndon_gather", "repair", "cdc"]
+
+
+class KolmVerifyError(KolmError):
+    """An encode call with verify on produced a payload that does not decode to its input
+    (KOLM_EVERIFY): .block / .method / .offset / .reason describe the lowest-numbered bad
+    block (reason 1 bytes differ, 2 the decoder rejected the payload), .report the whole
+    kolm_verify_report as a dict."""
+
+    def __init__(self, msg: str, report: dict):
+        super().__init__(KOLM_EVERIFY, msg)
+        self.report = report
+        self.block = report["first_bad_block"]
+        self.method = report["first_bad_method"]
+        self.offset = report["first_bad_offset"]
+        self.reason = report["first_bad_reason"]
 
 
 class KTime(ctypes.Structure):
@@ -78,6 +98,23 @@ class Stats(ctypes.Structure):
                                       "bytes": self.kt[i].bytes} for i in range(len(KT_NAMES))
                         if self.kt[i].launches}
         return d
+
+
+class VerifyReport(ctypes.Structure):
+    _fields_ = [
+        ("blocks", ctypes.c_uint32),
+        ("bad_blocks", ctypes.c_uint32),
+        ("first_bad_block", ctypes.c_uint32),
+        ("first_bad_method", ctypes.c_uint32),
+        ("first_bad_offset", ctypes.c_uint32),
+        ("first_bad_reason", ctypes.c_uint32),
+        ("bytes", ctypes.c_uint64),
+        ("ms_decode", ctypes.c_double),
+        ("ms_compare", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 _lib = None
@@ -133,6 +170,11 @@ SIGNATURES = [
     ("kolm_comm_barrier", I32, [P]),
     ("kolm_gather_payloads", I32, [P, P, U64, P, P, U32, I32, P, U64, U32, P, P, P, P, I32]),
     ("kolm_comm_wait", I32, [P]),
+    ("kolm_verify_blocks_device", I32, [P, P, P, U32, P, P, P, P, ctypes.POINTER(VerifyReport)]),
+    ("kolm_verify_container", I32, [P, U64, P, U64, P, U32, ctypes.POINTER(VerifyReport)]),
+    ("kolm_ctx_set_verify", I32, [P, I32]),
+    ("kolm_set_verify", I32, [I32]),
+    ("kolm_ctx_verify_report", I32, [P, ctypes.POINTER(VerifyReport)]),
 ]
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
@@ -177,10 +219,126 @@ def load():
     return _lib
 
 
-def check(rc: int):
+def check(rc: int, ctx=None):
     if rc != 0:
         msg = load().kolm_last_error()
-        raise KolmError(rc, msg.decode() if msg else "")
+        text = msg.decode() if msg else ""
+        if rc == KOLM_EVERIFY:
+            raise KolmVerifyError(text, verify_report(ctx))
+        raise KolmError(rc, text)
+
+
+def verify_report(ctx=None) -> dict:
+    """The verify report of ctx's (None: the default context's) last encode call that ran
+    with verify on (kolm_ctx_verify_report)."""
+    rep = VerifyReport()
+    rc = load().kolm_ctx_verify_report(ctx, ctypes.byref(rep))
+    if rc:
+        raise KolmError(rc, "kolm_ctx_verify_report")
+    return rep.as_dict()
+
+
+_last_verify: dict = {}
+_ENV_VERIFY = os.environ.get("KOLM_VERIFY", "0").strip() not in ("", "0")  # the contexts' own default
+
+
+class _verify_scope:
+    """Runs one native encode call with verify on, on ctx (None: the default context): the
+    switch is set and restored under _result_lock (the lock compress_fixed holds around its
+    call: every verified call of this binding is serialised by it), and the call's report is
+    kept for last_verify().  The switch goes back to what KOLM_VERIFY gave the context.
+    verify false: no lock, no call — the path as it was."""
+
+    def __init__(self, verify: bool, locked: bool = False, ctx=None):
+        self.verify, self.locked, self.ctx = bool(verify), locked, ctx
+
+    def _set(self, on: int) -> int:
+        L = load()
+        return L.kolm_set_verify(on) if self.ctx is None else L.kolm_ctx_set_verify(self.ctx, on)
+
+    def __enter__(self):
+        if self.verify:
+            if not self.locked:
+                _result_lock.acquire()
+            rc = self._set(1)
+            if rc:
+                if not self.locked:
+                    _result_lock.release()
+                check(rc)
+        return self
+
+    def __exit__(self, et, ev, tb):
+        global _last_verify
+        if self.verify:
+            try:
+                if et is None or isinstance(ev, KolmVerifyError):
+                    _last_verify = verify_report(self.ctx)
+                self._set(1 if _ENV_VERIFY else 0)
+            finally:
+                if not self.locked:
+                    _result_lock.release()
+        return False
+
+
+def last_verify() -> dict:
+    """Report of the last verified encode call made through this binding."""
+    return dict(_last_verify)
+
+
+def verify_blocks_device(ctx, d_data: int, bounds, d_payloads: int, payload_off, methods):
+    """kolm_verify_blocks_device: original and payloads device-resident.  Returns (first_bad
+    u32[nb]: offset of the block's first differing byte, KOLM_VERIFY_EQUAL or
+    KOLM_VERIFY_REJECTED; report dict)."""
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
+    off = np.ascontiguousarray(np.asarray(payload_off, dtype=np.uint64))
+    meth = np.ascontiguousarray(np.asarray(methods, dtype=np.uint32))
+    nb = len(meth)
+    if len(b) != nb + 1 or len(off) != nb + 1:
+        raise ValueError("bounds and payload_off must have one entry more than methods")
+    fb = np.zeros(max(nb, 1), dtype=np.uint32)
+    rep = VerifyReport()
+    check(load().kolm_verify_blocks_device(ctx, d_data, b.ctypes.data, nb, d_payloads, off.ctypes.data,
+                                           meth.ctypes.data, fb.ctypes.data, ctypes.byref(rep)))
+    return fb[:nb], rep.as_dict()
+
+
+def verify_blocks(data, bounds, payloads, methods, device: int = None, data_offset: int = 0):
+    """Uploads data (block i = data[bounds[i]:bounds[i+1]], bounds[0] = 0) and the blocks'
+    payloads, then checks on the device that every payload decodes to its block
+    (verify_blocks_device).  data_offset (0..15) places the data that many bytes into its
+    device buffer (any alignment is accepted).  Returns (first_bad, report)."""
+    dev = ensure_init() if device is None else device
+    ctx = device_ctx(dev)
+    data = bytes(data)
+    pay = b"".join(payloads)
+    off = np.zeros(len(payloads) + 1, dtype=np.uint64)
+    if payloads:
+        off[1:] = np.cumsum([len(p) for p in payloads])
+    dd = DeviceBuffer(ctx, data_offset + len(data) + 64)
+    dp = DeviceBuffer(ctx, len(pay) + 64)
+    try:
+        dd.upload(data, data_offset)
+        dp.upload(pay)
+        return verify_blocks_device(ctx, dd.ptr + data_offset, bounds, dp.ptr, off, methods)
+    finally:
+        dd.free()
+        dp.free()
+
+
+def verify_container(container, data):
+    """kolm_verify_container on the default context: (first_bad u32[nb] or None when the
+    lengths differ, report dict).  A malformed container raises ValueError as decompress does."""
+    ensure_init()
+    container, data = bytes(container), bytes(data)
+    fb = np.zeros(65536, dtype=np.uint32)
+    rep = VerifyReport()
+    rc = load().kolm_verify_container(container, len(container), data, len(data), fb.ctypes.data, len(fb),
+                                      ctypes.byref(rep))
+    if rc == KOLM_EFORMAT:
+        raise ValueError(load().kolm_last_error().decode())
+    check(rc)
+    r = rep.as_dict()
+    return (None if r["first_bad_reason"] == VR_LENGTH else fb[:r["blocks"]].copy()), r
 
 
 def device_count() -> int:
@@ -222,17 +380,19 @@ def device_ctx(device: int):
 
 
 def encode_blocks_device(ctx, d_data: int, n: int, block_size: int, d_arena: int, arena_cap: int,
-                         cand_mask: int = KOLM_DEFAULT_MASK):
+                         cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False):
     """Batched MDL encode of fixed blocks of the device buffer d_data[0, n) into the
-    device arena (kolm_encode_blocks_device).  Returns (sizes, method, offsets, stats)."""
+    device arena (kolm_encode_blocks_device).  Returns (sizes, method, offsets, stats).
+    verify: the batch is checked on ctx before the call returns (KolmVerifyError)."""
     nb = (n + block_size - 1) // block_size if n else 0
     sizes = np.zeros((max(nb, 1), KOLM_NCAND), dtype=np.uint32)
     method = np.zeros(max(nb, 1), dtype=np.uint32)
     off = np.zeros(nb + 1, dtype=np.uint64)
     st = Stats()
-    check(load().kolm_encode_blocks_device(ctx, d_data, n, block_size, cand_mask, None, d_arena, arena_cap,
-                                           sizes.ctypes.data, method.ctypes.data, off.ctypes.data,
-                                           ctypes.byref(st)))
+    with _verify_scope(verify, ctx=ctx):
+        check(load().kolm_encode_blocks_device(ctx, d_data, n, block_size, cand_mask, None, d_arena, arena_cap,
+                                               sizes.ctypes.data, method.ctypes.data, off.ctypes.data,
+                                               ctypes.byref(st)), ctx)
     return sizes[:nb], method[:nb], off, st.as_dict()
 
 
@@ -362,9 +522,11 @@ def bbwt_mtf_rice(data: bytes, flags: int, k: int = 2) -> bytes:
     return out.raw[:ln.value]
 
 
-def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, force=None):
+def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, force=None,
+                  verify: bool = False):
     """Batched MDL encode of fixed-size blocks.  Returns (sizes[nb,KOLM_NCAND], method[nb],
-    payloads list, stats dict)."""
+    payloads list, stats dict).  verify: check the payloads on the device before returning
+    (KolmVerifyError on a bad block)."""
     ensure_init()
     n = len(data)
     nb = (n + block_size - 1) // block_size if n else 0
@@ -383,17 +545,20 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MA
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    check(load().kolm_encode_blocks(
-        data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
-        fz.ctypes.data if fz is not None else None,
-        sizes.ctypes.data, method.ctypes.data, arena.ctypes.data, cap, off.ctypes.data,
-        ctypes.byref(st)))
+    with _verify_scope(verify):
+        check(load().kolm_encode_blocks(
+            data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
+            fz.ctypes.data if fz is not None else None,
+            sizes.ctypes.data, method.ctypes.data, arena.ctypes.data, cap, off.ctypes.data,
+            ctypes.byref(st)))
     payloads = [arena[int(off[i]):int(off[i + 1])].tobytes() for i in range(nb)]
     return sizes[:nb], method[:nb], payloads, st.as_dict()
 
 
-def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK):
-    """The whole KOLR container of data in fixed blocks (kolm_compress_fixed): (bytes, stats)."""
+def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False):
+    """The whole KOLR container of data in fixed blocks (kolm_compress_fixed): (bytes, stats).
+    verify: every device batch is checked before its payloads count (KolmVerifyError, no
+    container, on a bad block)."""
     ensure_init()
     n = len(data)
     src = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8) if n else np.zeros(1, np.uint8)
@@ -404,8 +569,11 @@ def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK):
     # copy out of it run under one lock (ctypes drops the GIL inside the call)
     with _result_lock:
         tc = time.perf_counter() if _HOST_PROF else 0.0
-        rc = load().kolm_compress_fixed(src.ctypes.data, n, block_size, cand_mask, ctypes.byref(out),
-                                        ctypes.byref(ln), ctypes.byref(st))
+        with _verify_scope(verify, locked=True):
+            rc = load().kolm_compress_fixed(src.ctypes.data, n, block_size, cand_mask, ctypes.byref(out),
+                                            ctypes.byref(ln), ctypes.byref(st))
+            if rc == KOLM_EVERIFY:
+                check(rc)
         if rc == KOLM_ERANGE:
             import struct
             raise struct.error(load().kolm_last_error().decode())
@@ -438,7 +606,7 @@ def _new_bytes(n: int) -> bytes:
     return _PyBytes_New(None, n) if n else b""
 
 
-def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, force=None):
+def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, force=None, verify: bool = False):
     """Batched MDL encode of content-defined blocks: block i = data[bounds[i]:bounds[i+1]]
     (bounds[0] = 0, strictly increasing, bounds[-1] = len(data)).  Same return value as
     encode_blocks."""
@@ -461,11 +629,12 @@ def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, f
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    check(load().kolm_encode_blocks(
-        data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
-        fz.ctypes.data if fz is not None else None,
-        sizes.ctypes.data, method.ctypes.data, arena.ctypes.data, cap, off.ctypes.data,
-        ctypes.byref(st)))
+    with _verify_scope(verify):
+        check(load().kolm_encode_blocks(
+            data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
+            fz.ctypes.data if fz is not None else None,
+            sizes.ctypes.data, method.ctypes.data, arena.ctypes.data, cap, off.ctypes.data,
+            ctypes.byref(st)))
     payloads = [arena[int(off[i]):int(off[i + 1])].tobytes() for i in range(nb)]
     return sizes[:nb], method[:nb], payloads, st.as_dict()
 
@@ -482,7 +651,8 @@ def cdc_boundaries(data: bytes, min_size: int, avg_size: int, max_size: int, mer
     return starts[:cnt.value + 1] if cnt.value else starts[:0]
 
 
-def encode_blocks_multi(data: bytes, block_size: int, ngpu: int, cand_mask: int = KOLM_DEFAULT_MASK):
+def encode_blocks_multi(data: bytes, block_size: int, ngpu: int, cand_mask: int = KOLM_DEFAULT_MASK,
+                        verify: bool = False):
     """encode_blocks over ngpu devices of this process (contiguous block shards, one host
     thread per device; kolm_encode_blocks_multi).  Same return value."""
     ensure_init()
@@ -494,8 +664,9 @@ def encode_blocks_multi(data: bytes, block_size: int, ngpu: int, cand_mask: int 
     cap = 9 * n + 64 * nb + 64
     arena = np.zeros(cap, dtype=np.uint8)
     st = Stats()
-    check(load().kolm_encode_blocks_multi(
-        int(ngpu), data, n, block_size, cand_mask, None, sizes.ctypes.data, method.ctypes.data,
-        arena.ctypes.data, cap, off.ctypes.data, ctypes.byref(st)))
+    with _verify_scope(verify):
+        check(load().kolm_encode_blocks_multi(
+            int(ngpu), data, n, block_size, cand_mask, None, sizes.ctypes.data, method.ctypes.data,
+            arena.ctypes.data, cap, off.ctypes.data, ctypes.byref(st)))
     payloads = [arena[int(off[i]):int(off[i + 1])].tobytes() for i in range(nb)]
     return sizes[:nb], method[:nb], payloads, st.as_dict()

@@ -340,14 +340,21 @@ def assemble_container(block_size: int, total_len: int, per_rank_ids: Sequence[S
 
 def compress_blocks_fixed_distributed(data: bytes, block_size: int, comm=None, dst: int = 0,
                                       cand_mask: Optional[int] = None,
-                                      partition: str = "contiguous") -> Optional[bytes]:
+                                      partition: str = "contiguous",
+                                      verify: Optional[bool] = None) -> Optional[bytes]:
     """Every rank calls this with the same `data`; rank r encodes its blocks
     (rank_blocks(.., partition)) on its GPU into a device arena (kolm_encode_blocks_device),
     the arenas, method ids and offsets are gathered onto `dst` (comm.gather_payloads; RCCL
     over xGMI by default), and `dst` returns the container (others return None) —
     bit-identical to compress_blocks_fixed(data) for either partition.  Only `dst` copies
-    payloads to the host, once, to write the container."""
+    payloads to the host, once, to write the container.  `verify` (default kolm.G_VERIFY):
+    each rank checks its own shard on its device before the gather; the ranks then agree on
+    the outcome (one all-reduce) and every rank raises when any shard failed — the rank that
+    owns the bad block a KolmVerifyError with the block numbered within its shard."""
     from . import _lib, candidate_mask
+    import kolm as _k
+    verify = _k.G_VERIFY if verify is None else bool(verify)
+    failure = None
     if block_size <= 0:
         raise ValueError("block_size must be positive")
     comm = default_comm() if comm is None else comm
@@ -367,10 +374,23 @@ def compress_blocks_fixed_distributed(data: bytes, block_size: int, comm=None, d
     arena = _lib.DeviceBuffer(ctx, _lib.arena_capacity(m, len(mine), mask))
     if m:
         d_in = _lib.input_buffer(ctx, part)
-        _, method, off, _ = _lib.encode_blocks_device(ctx, d_in.ptr, m, block_size, arena.ptr, arena.nbytes, mask)
+        if verify:
+            try:
+                _, method, off, _ = _lib.encode_blocks_device(ctx, d_in.ptr, m, block_size, arena.ptr, arena.nbytes,
+                                                              mask, verify=True)
+            except _lib.KolmVerifyError as e:  # stay in step with the other ranks' collectives
+                failure = e
+                method, off = np.zeros(0, np.uint32), np.zeros(1, np.uint64)
+        else:
+            _, method, off, _ = _lib.encode_blocks_device(ctx, d_in.ptr, m, block_size, arena.ptr, arena.nbytes, mask)
         d_in.free()
     else:
         method, off = np.zeros(0, np.uint32), np.zeros(1, np.uint64)
+    if verify:
+        if int(comm.allreduce(np.array([1 if failure else 0], np.uint64), op="max")[0]):
+            if failure is not None:
+                raise failure
+            raise _lib.KolmError(_lib.KOLM_EVERIFY, "another rank's shard failed verification")
     g = comm.gather_payloads(arena.ptr, int(off[-1]), method, off, dst=dst, dst_cap_blocks=max(nb, 1))
     if rank != dst:
         return None
