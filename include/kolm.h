@@ -18,6 +18,10 @@
  *                             context per device).
  *   kolm_toc_write / kolm_toc_read: the KOLR container's header + TOC on the host
  *                             (PY:2375-2445 writer, PY:2451-2530 reader; kolm_toc.cpp).
+ *   kolm_reader_* / kolm_range_plan: random-access reads of a container (PY has no
+ *                             equivalent: decompress, PY:2451-2550, decodes every block): only
+ *                             the blocks a byte range touches are decoded, the ranges are packed
+ *                             on the device (k_range.hip, kolm_range.cpp).
  *   kolm_comm_* / kolm_gather_payloads: RCCL over xGMI (kolm_comm.cpp) — the reassembly
  *                             of independently encoded block shards (PY:2350-2369 blocks,
  *                             PY:2375-2445 the container they feed) onto one rank.
@@ -336,6 +340,78 @@ int kolm_set_verify(int enable);  /* default context */
 /* The report accumulated over the batches of the last encode call of ctx (NULL: the default
  * context) that ran with verify enabled. */
 int kolm_ctx_verify_report(kolm_ctx* ctx, kolm_verify_report* rep);
+
+/* ---- random-access reads: decode only the blocks a byte range touches --------------- */
+/* A KOLR container's blocks are coded independently and its TOC gives every block's geometry,
+ * method and payload offset, so a byte range of the decoded stream needs only the blocks it
+ * touches: they are decoded into scratch on the device (the decoders of kolm_decode_blocks) and
+ * k_range_gather packs the requested bytes, back to back in request order, into the output. */
+typedef struct kolm_range_seg {
+    uint64_t src;  /* offset in the group's decoded scratch (its selected blocks back to back) */
+    uint64_t dst;  /* offset in the packed output */
+    uint64_t len;
+} kolm_range_seg;
+/* The plan of a read (host only: no device call, usable without a GPU): blocks of orig_lens[i]
+ * decoded bytes each, nranges ranges [offs[r], offs[r] + lens[r]) of the decoded stream.
+ *   sel          the blocks that hold a byte of a range, ascending, each once
+ *   group_first  [ngroups + 1]: group g = sel[group_first[g], group_first[g + 1]).  Consecutive
+ *                selected blocks share a group while their decoded bytes stay at or under
+ *                min(2^31 - 1, group_limit); group_limit 0 = $KOLM_READ_BYTES (read per call), else
+ *                1 GiB.  A single block always forms a group.
+ *   run_first    [nruns + 1]: run r = sel[run_first[r], run_first[r + 1]), blocks consecutive in
+ *                the container (contiguous payloads); a run lies inside one group
+ *   group_seg    [ngroups + 1]: group g's copy segments = segs[group_seg[g], group_seg[g + 1]),
+ *                in request order; a range that has bytes in several groups has one segment in
+ *                each, an empty range none.  The output is the ranges back to back.
+ * caps[4] = entries available: sel, groups (group_first and group_seg hold one more), runs
+ * (run_first holds one more), segs; counts[4] receives what the plan needs, in that order.
+ * KOLM_EARG (message names the range) when a range does not lie inside [0, total_len], before
+ * anything else; KOLM_ECAP (counts filled) when an array is too small or caps is NULL. */
+int kolm_range_plan(const uint32_t* orig_lens, uint32_t nblocks, const uint64_t* offs, const uint64_t* lens,
+                    uint32_t nranges, uint64_t group_limit, uint32_t* sel, uint32_t* group_first,
+                    uint32_t* run_first, uint32_t* group_seg, kolm_range_seg* segs, const uint64_t* caps,
+                    uint64_t* counts);
+
+typedef struct kolm_reader kolm_reader;
+typedef struct kolm_read_stats {
+    uint32_t ranges;          /* ranges of the call */
+    uint32_t blocks_decoded;  /* selected blocks */
+    uint32_t groups;          /* decode batches */
+    uint32_t compactions;     /* groups whose payload runs were gathered into a staging buffer first */
+    uint64_t bytes_returned;  /* the packed output */
+    uint64_t bytes_decoded;   /* decoded bytes of the selected blocks */
+    double ms_decode;         /* device time of the decode kernels (HIP events) */
+    double ms_gather;         /* device time of k_range_gather, both uses */
+} kolm_read_stats;
+/* Opens container[0, cn) for reading on ctx (NULL: the default context): kolm_toc_read first
+ * (KOLM_EFORMAT / KOLM_ERANGE with PY's message, as there), then the payload area goes up once
+ * and stays resident until kolm_reader_close; the container's bytes are not needed afterwards.
+ * Blocks the device does not decode (method ids outside KOLM_DECODE_MASK, id-10 blocks of 2^28
+ * bytes or more) do not fail the open: they matter when a read selects them.  Close every
+ * reader before its context is destroyed.  Several readers may share a context; every call
+ * holds the context's lock. */
+int kolm_reader_open(kolm_ctx* ctx, const uint8_t* container, uint64_t cn, kolm_reader** out);
+int kolm_reader_close(kolm_reader* r);
+/* info[5] = {mode, size_field, total_len, nblocks, payload bytes}; methods / orig_lens (optional,
+ * cap entries each; KOLM_ECAP when cap < nblocks and either is given). */
+int kolm_reader_info(kolm_reader* r, uint64_t* info, uint32_t* methods, uint32_t* orig_lens, uint32_t cap);
+/* Reads nranges byte ranges of the decoded stream into out[0, out_cap) (host), back to back in
+ * request order (range r at the sum of lens[0, r)): plan (kolm_range_plan), then per group the
+ * payload runs are compacted into a staging buffer when there are several (one run is decoded
+ * where it lies), the group's blocks are decoded into scratch and k_range_gather packs the
+ * group's segments into a device buffer; one copy brings the packed bytes to the host.  The
+ * decoded scratch never leaves the device.  Every argument is checked before the first launch:
+ * KOLM_EARG for a range outside [0, total_len] (message names the range) and for a selected
+ * block the device does not decode (message names the container's block number and method);
+ * KOLM_ECAP when the ranges' bytes exceed out_cap.  A selected block whose decoder rejects its
+ * payload: KOLM_EARG, the block and method named.  Blocks no range touches do not matter.
+ * stats optional. */
+int kolm_reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges, uint8_t* out,
+                     uint64_t out_cap, kolm_read_stats* stats);
+/* The same with the packed output left in device memory d_out[0, out_cap) (any alignment; only
+ * the ranges' bytes are written). */
+int kolm_reader_read_device(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges,
+                            void* d_out, uint64_t out_cap, kolm_read_stats* stats);
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (kolm_comm.cpp) ------------- */
 /* The only data exchange of the multi-GPU path: blocks are independent (PY:2350-2369), so

@@ -2901,6 +2901,242 @@ int kolm_verify_container(const uint8_t* container, uint64_t cn, const uint8_t* 
     return rc;
 }
 
+}  // extern "C"
+
+// ---- random-access reads: decode the blocks a range touches, pack the ranges on the device ----
+struct kolm_reader {
+    kolm_ctx* c = nullptr;
+    u32 mode = 0, size_field = 0, nb = 0;
+    u64 total = 0, pbytes = 0;
+    std::vector<u32> methods, lens;
+    std::vector<u64> poff, starts;  // payload offsets / decoded block starts, nb + 1 entries each
+    // the payload area, resident (its own allocation: it outlives the calls).  A source of
+    // k_range_gather (payload compaction): hipMalloc aligns it to 256 bytes and it is padded by
+    // 64 + 16 bytes, the decoders' read-ahead plus the gather's last aligned word.
+    u8* dpay = nullptr;
+};
+
+namespace {
+
+// Uploads a segment table with the exclusive scan of its item counts and launches k_range_gather
+// on c->stream between the event pair (e0, e1).  dst: the segments' destination base.
+void gather_segments(kolm_ctx* c, const char* name, const u8* src, u8* dst, const rng::Seg* segs, u32 nseg,
+                     std::vector<u32>& scan, hipEvent_t e0, hipEvent_t e1) {
+    hipStream_t s = c->stream;
+    scan.assign((size_t)nseg + 1, 0);
+    u64 items = 0, bytes = 0;
+    for (u32 i = 0; i < nseg; ++i) {
+        const u32 dmis = (u32)((reinterpret_cast<uintptr_t>(dst) + segs[i].dst) & (rng::WORD - 1));
+        items += rng::items(dmis, segs[i].len);
+        bytes += segs[i].len;
+        if (items > 0xFFFFFFFFull) throw kolm::HipError(hipErrorInvalidValue, "more than 2^32 - 1 gather items", __LINE__);
+        scan[i + 1] = (u32)items;
+    }
+    const std::string nseg_name = std::string(name) + "_seg", nscan_name = std::string(name) + "_scan";
+    rng::Seg* dseg = c->get<rng::Seg>(nseg_name.c_str(), nseg);
+    u32* dscan = c->get<u32>(nscan_name.c_str(), (size_t)nseg + 1);
+    KOLM_HIP_CHECK(hipMemcpyAsync(dseg, segs, sizeof(rng::Seg) * nseg, hipMemcpyHostToDevice, s));
+    KOLM_HIP_CHECK(hipMemcpyAsync(dscan, scan.data(), sizeof(u32) * ((size_t)nseg + 1), hipMemcpyHostToDevice, s));
+    KOLM_HIP_CHECK(hipEventRecord(e0, s));
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_range_gather", 2 * bytes);
+        launch_range_gather(src, dst, dseg, dscan, nseg, items, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(e1, s));
+}
+
+// out (host) or d_out (device) receives the packed ranges.  Context lock not held on entry.
+int reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nr, uint8_t* out, void* d_out,
+                uint64_t out_cap, kolm_read_stats* stats) {
+    if (stats) *stats = kolm_read_stats{};
+    if (!r || !r->c || (nr && (!offs || !lens))) return KOLM_EARG;
+    // every argument check before the first launch: the plan (ranges), the output, the selected blocks
+    RangePlan p;
+    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, offs, lens, nr, 0, p)) return rc;
+    u64 want = 0;
+    for (u32 i = 0; i < nr; ++i) want += lens[i];
+    if (want > out_cap) {
+        set_err("output capacity too small");
+        return KOLM_ECAP;
+    }
+    if (want && !out && !d_out) return KOLM_EARG;
+    kolm_read_stats st{};
+    st.ranges = nr;
+    st.bytes_returned = want;
+    st.blocks_decoded = (u32)p.sel.size();
+    st.groups = (u32)p.group_first.size() - 1;
+    for (u32 b : p.sel) {
+        const u32 m = r->methods[b];
+        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
+            r->lens[b] >= (1u << 31)) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        st.bytes_decoded += r->lens[b];
+    }
+    if (p.sel.empty()) {
+        if (stats) *stats = st;
+        return KOLM_OK;
+    }
+    kolm_ctx* c = r->c;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        hipStream_t s = c->stream;
+        c->active = s;
+        u8* dout = d_out ? static_cast<u8*>(d_out) : c->get<u8>("rd_out", want + 64);
+        std::vector<u32> gm, gl, status, scan;
+        std::vector<u64> gp;
+        std::vector<rng::Seg> runs;
+        for (u32 g = 0; g + 1 < p.group_first.size(); ++g) {
+            const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
+            gm.resize(n), gl.resize(n), gp.assign((size_t)n + 1, 0);
+            runs.clear();
+            u64 tot = 0;
+            for (u32 i = i0; i < i1; ++i) {
+                const u32 b = p.sel[i];
+                gm[i - i0] = r->methods[b];
+                gl[i - i0] = r->lens[b];
+                tot += r->lens[b];
+                const u64 plen = r->poff[b + 1] - r->poff[b];
+                if (i == i0 || b != p.sel[i - 1] + 1) runs.push_back(rng::Seg{r->poff[b] - r->poff[0], gp[i - i0], 0});
+                runs.back().len += plen;
+                gp[i - i0 + 1] = gp[i - i0] + plen;
+            }
+            // one run is decoded where it lies; several are gathered into a staging buffer first
+            // (decode_batch takes contiguous payloads).  "rd_pay": read-ahead padding as dec_pay.
+            const u8* pay = r->dpay + runs[0].src;
+            const bool compact = runs.size() > 1;
+            if (compact) {
+                u8* stage = c->get<u8>("rd_pay", gp[n] + 64);
+                gather_segments(c, "rd_c", r->dpay, stage, runs.data(), (u32)runs.size(), scan, c->ev[4], c->ev[5]);
+                pay = stage;
+                ++st.compactions;
+            }
+            // the decode scratch, a source of k_range_gather: 256-byte aligned (hipMalloc), padded
+            // by the decoders' 64 bytes and the gather's last aligned 16-byte word
+            u8* dec = c->get<u8>("rd_dec", tot + 64 + rng::WORD);
+            double ms = 0.0;
+            if (int e = decode_batch(c, pay, gp.data(), gm.data(), gl.data(), n, tot, dec, &ms, &status)) return e;
+            st.ms_decode += ms;
+            if (compact) st.ms_gather += ev_ms(c->ev[4], c->ev[5]);  // retired: decode_batch drained the stream
+            for (u32 i = 0; i < n; ++i)
+                if (status[i]) {
+                    char msg[128];
+                    snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], gm[i],
+                             status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
+                    set_err(msg);
+                    return KOLM_EARG;
+                }
+            const u32 s0 = p.group_seg[g], s1 = p.group_seg[g + 1];
+            if (s1 > s0) {
+                gather_segments(c, "rd_g", dec, dout, p.segs.data() + s0, s1 - s0, scan, c->ev[2], c->ev[3]);
+                c->sync();  // the next group reuses the scratch tables; the events are retired
+                st.ms_gather += ev_ms(c->ev[2], c->ev[3]);
+            }
+        }
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        if (!d_out && want) KOLM_HIP_CHECK(hipMemcpy(out, dout, want, hipMemcpyDeviceToHost));
+        return KOLM_OK;
+    });
+    if (stats) *stats = st;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kolm_reader_open(kolm_ctx* c, const uint8_t* container, uint64_t cn, kolm_reader** out) {
+    if (!out) return KOLM_EARG;
+    *out = nullptr;
+    if (!c) c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    if (!container && cn) return KOLM_EARG;
+    u32 fields[4] = {};
+    u64 start = 0;
+    std::vector<u32> methods(65536), lens(65536);
+    std::vector<u64> poff(65537);
+    if (int rc = kolm_toc_read(container, cn, fields, &start, methods.data(), lens.data(), poff.data(), 65536)) return rc;
+    std::unique_ptr<kolm_reader> r(new kolm_reader);
+    r->c = c;
+    r->mode = fields[0], r->size_field = fields[1], r->total = fields[2], r->nb = fields[3];
+    methods.resize(r->nb), lens.resize(r->nb), poff.resize((size_t)r->nb + 1);
+    r->starts.assign((size_t)r->nb + 1, 0);
+    for (u32 i = 0; i < r->nb; ++i) r->starts[i + 1] = r->starts[i] + lens[i];
+    if (r->starts[r->nb] != r->total) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "Length mismatch: got %llu, expect %llu", (unsigned long long)r->starts[r->nb],
+                 (unsigned long long)r->total);
+        set_err(msg);
+        return KOLM_EFORMAT;
+    }
+    for (u32 i = 0; i < r->nb; ++i)
+        if (poff[i + 1] < poff[i]) return KOLM_EFORMAT;
+    r->methods.swap(methods), r->lens.swap(lens), r->poff.swap(poff);
+    r->pbytes = r->nb ? r->poff[r->nb] - r->poff[0] : 0;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        KOLM_HIP_CHECK(hipMalloc((void**)&r->dpay, r->pbytes + 64 + rng::WORD));
+        if (r->pbytes) {
+            const hipError_t e = hipMemcpy(r->dpay, container + start + r->poff[0], r->pbytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(r->dpay);
+                r->dpay = nullptr;
+                KOLM_HIP_CHECK(e);
+            }
+        }
+        return KOLM_OK;
+    });
+    if (rc) return rc;
+    *out = r.release();
+    return KOLM_OK;
+}
+
+int kolm_reader_close(kolm_reader* r) {
+    if (!r) return KOLM_EARG;
+    kolm_ctx* c = r->c;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        if (r->dpay) KOLM_HIP_CHECK(hipFree(r->dpay));
+        return KOLM_OK;
+    });
+    delete r;
+    return rc;
+}
+
+int kolm_reader_info(kolm_reader* r, uint64_t* info, uint32_t* methods, uint32_t* orig_lens, uint32_t cap) {
+    if (!r || !info) return KOLM_EARG;
+    info[0] = r->mode, info[1] = r->size_field, info[2] = r->total, info[3] = r->nb, info[4] = r->pbytes;
+    if ((methods || orig_lens) && cap < r->nb) {
+        set_err("kolm_reader_info: capacity too small");
+        return KOLM_ECAP;
+    }
+    if (methods) std::copy(r->methods.begin(), r->methods.end(), methods);
+    if (orig_lens) std::copy(r->lens.begin(), r->lens.end(), orig_lens);
+    return KOLM_OK;
+}
+
+int kolm_reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges, uint8_t* out,
+                     uint64_t out_cap, kolm_read_stats* stats) {
+    return reader_read(r, offs, lens, nranges, out, nullptr, out_cap, stats);
+}
+
+int kolm_reader_read_device(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges, void* d_out,
+                            uint64_t out_cap, kolm_read_stats* stats) {
+    if (!d_out && nranges) {
+        u64 want = 0;
+        for (u32 i = 0; offs && lens && i < nranges; ++i) want += lens[i];
+        if (want) return KOLM_EARG;
+    }
+    return reader_read(r, offs, lens, nranges, nullptr, d_out, out_cap, stats);
+}
+
 int kolm_bbwt_forward(const uint8_t* in, size_t n, uint8_t* out) {
     kolm_ctx* c = need_default();
     if (!c) return KOLM_ENOINIT;

@@ -625,6 +625,35 @@ void launch_verify_flip(u8* p, hipStream_t s);  // *p ^= 0x80 (KOLM_VERIFY_INJEC
 
 }  // namespace kolm
 
+// ---- k_range.hip / kolm_range.cpp: random-access reads (range_core.h) ----
+#include <vector>
+
+#include "range_core.h"
+namespace kolm {
+// nseg segments (device table segs, offsets into src / dst) with the exclusive scan of their item
+// counts (device, nseg + 1 words; scan[nseg] = nitems).  Writes bytes of the segments'
+// destinations only; reads the aligned 16-byte source words that hold a byte of a segment.
+void launch_range_gather(const u8* src, u8* dst, const rng::Seg* segs, const u32* scan, u32 nseg, u64 nitems,
+                         hipStream_t s);
+// What a read of nranges byte ranges decodes and copies (kolm_range_plan, include/kolm.h):
+//   sel          the selected blocks, ascending
+//   group_first  [ngroups + 1] group g = sel[group_first[g], group_first[g + 1])
+//   run_first    [nruns + 1] run r = sel[run_first[r], run_first[r + 1]): blocks consecutive in the
+//                container; a run never crosses a group edge
+//   group_seg    [ngroups + 1] group g's copy segments = segs[group_seg[g], group_seg[g + 1])
+//   segs         src = offset in the group's decoded scratch (its blocks back to back), dst =
+//                offset in the packed output
+struct RangePlan {
+    std::vector<u32> sel, group_first, run_first, group_seg;
+    std::vector<rng::Seg> segs;
+};
+u64 range_group_limit(u64 limit);  // 0: $KOLM_READ_BYTES or 1 GiB; capped at 2^31 - 1
+// starts: [nblocks + 1] prefix of orig_lens.  KOLM_EARG (message names the range) when a range
+// leaves [0, total_len].
+int range_plan(const u32* orig_lens, const u64* starts, u32 nblocks, const u64* offs, const u64* lens, u32 nranges,
+               u64 limit, RangePlan& p);
+}  // namespace kolm
+
 #define KOLM_HIP_CHECK(x)                                              \
     do {                                                               \
         hipError_t e_ = (x);                                           \

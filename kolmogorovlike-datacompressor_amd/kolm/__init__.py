@@ -6,6 +6,9 @@ Drop-in for the reference's block API (PY = final_researched/kolm_final_research
     compress_blocks_cdc(data, min_size, avg_size, max_size)    PY:2213-2326
     cdc_fast_boundaries_strict(data, min, avg, max, merge)     PY:210-309
     decompress(container) -> bytes                             PY:2451-2550
+    open_container(container) -> Reader                        (not in PY: byte ranges of a
+                                                               container, only the touched
+                                                               blocks decoded, on the device)
     _select_encoders() / _select_decoders()                    PY:2152-2207
     bbwt_forward, mtf_encode, rice_encode, encode_lz77,
     encode_bbwt_mtf_rice, encode_raw, encode_xor,
@@ -31,6 +34,7 @@ ids unchanged, containers still decodable by the reference).
 from __future__ import annotations
 
 import struct
+import sys
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 from . import _lib
@@ -45,6 +49,7 @@ __all__ = [
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
+    "open_container", "Reader", "last_read",
 ]
 
 CANDIDATE_NAMES = ["raw", "xor", "bbwt", "bbwt_bp", "bbwt_nib", "bbwt_br", "bbwt_gray", "lz77",
@@ -384,6 +389,171 @@ def decompress(container: bytes, device: bool = True) -> bytes:
     if len(out) != total_len:
         raise ValueError(f"Length mismatch: got {len(out)}, expect {total_len}")
     return bytes(out)
+
+
+def last_read() -> Dict[str, Any]:
+    """kolm_read_stats of the last Reader call: ranges, bytes_returned, blocks_decoded,
+    bytes_decoded, groups, compactions, ms_decode, ms_gather (a call served by the host
+    decoders reports its blocks and bytes with groups = 0 and "host": True)."""
+    return dict(_last_read) if _last_read.get("host") else _lib.last_read()
+
+
+_last_read: Dict[str, Any] = {}
+
+
+class Reader:
+    """Random-access reads of a KOLR container (not in PY): open_container() parses the TOC
+    and keeps the payload area resident on the device; every read decodes only the blocks its
+    ranges touch, packs the requested bytes on the device (k_range_gather) and brings back
+    nothing else.  A context manager; close() frees the resident payloads.
+
+    Blocks the device does not decode — a method id outside KOLM_DECODE_MASK, an id-10 block
+    with a Rice parameter byte above 15 or of 2^28 bytes or more, the cases decompress() gives
+    to the host decoders — are found at open; a call whose ranges touch one is served by
+    kolm.decode.decode_block on the host, for that call (same bytes; no speed claimed)."""
+
+    def __init__(self, container: bytes, ctx=None):
+        blob = bytes(container)
+        self._h, info = _lib.reader_open(blob, ctx)
+        self.mode, self.size_field = info["mode"], info["size_field"]
+        self._total = info["total_len"]
+        starts, pos = [], 0
+        for n in info["orig_lens"]:
+            starts.append(pos)
+            pos += n
+        self._starts = starts + [pos]
+        self.blocks: List[Tuple[int, int, int]] = list(zip(starts, info["orig_lens"], info["methods"]))
+        # host-only blocks (the container's bytes are kept only when there is one)
+        self._host_blocks: List[int] = []
+        self._blob: Optional[bytes] = None
+        need_payload = [i for i, (_, n, m) in enumerate(self.blocks) if m == 10 and n]
+        if need_payload or any(not (_lib.KOLM_DECODE_MASK >> m) & 1 for _, _, m in self.blocks):
+            payloads = read_container(blob)[5]
+            self._host_blocks = [i for i, (_, n, m) in enumerate(self.blocks) if n and (
+                not (_lib.KOLM_DECODE_MASK >> m) & 1
+                or (m == 10 and (n >= _V2_DEVICE_MAX or _v2_k_above_15(payloads[i]))))]
+            if self._host_blocks:
+                self._blob = blob
+
+    def __len__(self) -> int:
+        return self._total
+
+    def __enter__(self) -> "Reader":
+        return self
+
+    def __exit__(self, *exc) -> bool:
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if not sys.is_finalizing():  # at interpreter exit the runtime goes down with the process
+                self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            _lib.reader_close(h)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("I/O operation on closed reader")
+        return self._h
+
+    def _check(self, ranges) -> List[Tuple[int, int]]:
+        out = []
+        for i, (o, n) in enumerate(ranges):
+            o, n = int(o), int(n)
+            if o < 0 or n < 0 or o + n > self._total:
+                raise ValueError(f"range {i}: [{o}, +{n}) is not inside the container's {self._total} bytes")
+            out.append((o, n))
+        return out
+
+    def _touches_host_block(self, ranges) -> bool:
+        for o, n in ranges:
+            for b in self._host_blocks:
+                s, ln, _ = self.blocks[b]
+                if n and o < s + ln and o + n > s:
+                    return True
+        return False
+
+    def _read_host(self, ranges) -> List[bytes]:
+        """The ranges through the host decoders: every touched block decoded once."""
+        import bisect
+        global _last_read
+        _, _, _, mids, orig, payloads = read_container(self._blob)
+        dec: Dict[int, bytes] = {}
+        out = []
+        for o, n in ranges:
+            piece = bytearray()
+            if n:
+                b = bisect.bisect_right(self._starts, o) - 1
+                while b < len(mids) and self._starts[b] < o + n:
+                    if orig[b]:
+                        if b not in dec:
+                            dec[b] = decode_block(mids[b], payloads[b], orig[b])
+                        lo, hi = max(o, self._starts[b]), min(o + n, self._starts[b + 1])
+                        piece += dec[b][lo - self._starts[b]:hi - self._starts[b]]
+                    b += 1
+            out.append(bytes(piece))
+        _last_read = {"host": True, "ranges": len(ranges), "bytes_returned": sum(n for _, n in ranges),
+                      "blocks_decoded": len(dec), "bytes_decoded": sum(len(v) for v in dec.values()), "groups": 0,
+                      "compactions": 0, "ms_decode": 0.0, "ms_gather": 0.0}
+        return out
+
+    def read_many(self, ranges) -> List[bytes]:
+        """The bytes of every (offset, length) in `ranges`, as a list.  Strict: a range outside
+        the data raises ValueError before anything is launched.  One device call serves the
+        whole list; its packed result is sliced on the host."""
+        global _last_read
+        h = self._handle()
+        ranges = self._check(ranges)
+        if self._host_blocks and self._touches_host_block(ranges):
+            return self._read_host(ranges)
+        _last_read = {}
+        packed = _lib.reader_read(h, ranges)
+        out, pos = [], 0
+        for _, n in ranges:
+            out.append(packed[pos:pos + n])
+            pos += n
+        return out
+
+    def read(self, offset: int = 0, size: int = -1) -> bytes:
+        """Like a file's read at `offset`: at most `size` bytes (all the rest when negative),
+        clipped at the end of the data."""
+        self._handle()
+        if offset < 0:
+            raise ValueError("negative offset")
+        offset = min(int(offset), self._total)
+        n = self._total - offset if size is None or size < 0 else min(int(size), self._total - offset)
+        return self.read_many([(offset, n)])[0]
+
+    def read_many_device(self, ranges, dptr: int, cap: int) -> List[int]:
+        """The ranges' bytes packed back to back at the device address dptr (cap bytes
+        available), left on the device; returns every range's offset in that buffer.  Ranges
+        that touch a host-only block raise ValueError here (there is no device result)."""
+        global _last_read
+        h = self._handle()
+        ranges = self._check(ranges)
+        if self._host_blocks and self._touches_host_block(ranges):
+            raise ValueError("a range touches a block the device does not decode")
+        if sum(n for _, n in ranges) > cap:
+            raise ValueError("the ranges' bytes exceed the device buffer")
+        _last_read = {}
+        _lib.reader_read_device(h, ranges, dptr, cap)
+        offs, pos = [], 0
+        for _, n in ranges:
+            offs.append(pos)
+            pos += n
+        return offs
+
+
+def open_container(container: bytes, ctx=None) -> Reader:
+    """A Reader over `container` (see Reader).  ctx (optional): a context of kolm._lib.device_ctx
+    instead of the default one.  A malformed container raises what decompress raises."""
+    return Reader(container, ctx)
 
 
 def verify(container: bytes, data: bytes) -> Dict[str, Any]:

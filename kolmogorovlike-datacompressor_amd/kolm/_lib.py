@@ -117,6 +117,26 @@ class VerifyReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ReadStats(ctypes.Structure):
+    _fields_ = [
+        ("ranges", ctypes.c_uint32),
+        ("blocks_decoded", ctypes.c_uint32),
+        ("groups", ctypes.c_uint32),
+        ("compactions", ctypes.c_uint32),
+        ("bytes_returned", ctypes.c_uint64),
+        ("bytes_decoded", ctypes.c_uint64),
+        ("ms_decode", ctypes.c_double),
+        ("ms_gather", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RangeSeg(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_uint64), ("dst", ctypes.c_uint64), ("len", ctypes.c_uint64)]
+
+
 _lib = None
 _lock = threading.Lock()
 _result_lock = threading.Lock()  # kolm_compress_fixed's result buffer (see compress_fixed)
@@ -175,6 +195,12 @@ SIGNATURES = [
     ("kolm_ctx_set_verify", I32, [P, I32]),
     ("kolm_set_verify", I32, [I32]),
     ("kolm_ctx_verify_report", I32, [P, ctypes.POINTER(VerifyReport)]),
+    ("kolm_range_plan", I32, [P, U32, P, P, U32, U64, P, P, P, P, P, P, P]),
+    ("kolm_reader_open", I32, [P, P, U64, ctypes.POINTER(P)]),
+    ("kolm_reader_close", I32, [P]),
+    ("kolm_reader_info", I32, [P, P, P, P, U32]),
+    ("kolm_reader_read", I32, [P, P, P, U32, P, U64, ctypes.POINTER(ReadStats)]),
+    ("kolm_reader_read_device", I32, [P, P, P, U32, P, U64, ctypes.POINTER(ReadStats)]),
 ]
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
@@ -670,3 +696,115 @@ def encode_blocks_multi(data: bytes, block_size: int, ngpu: int, cand_mask: int 
             arena.ctypes.data, cap, off.ctypes.data, ctypes.byref(st)))
     payloads = [arena[int(off[i]):int(off[i + 1])].tobytes() for i in range(nb)]
     return sizes[:nb], method[:nb], payloads, st.as_dict()
+
+
+# ---- random-access reads (kolm_range_plan, kolm_reader_*) ----------------------------------
+
+def _ranges_arrays(ranges):
+    """[(offset, length), ...] -> (offs u64[n], lens u64[n]); negative values raise ValueError."""
+    offs = np.zeros(max(len(ranges), 1), dtype=np.uint64)
+    lens = np.zeros(max(len(ranges), 1), dtype=np.uint64)
+    for i, (o, n) in enumerate(ranges):
+        if o < 0 or n < 0:
+            raise ValueError(f"range {i}: negative offset or length")
+        offs[i], lens[i] = o, n
+    return offs, lens
+
+
+def range_plan(orig_lens, ranges, group_limit: int = 0) -> dict:
+    """kolm_range_plan (host only, no device): which blocks a read of `ranges` decodes and how
+    the decoded bytes are packed.  Returns {"sel": [block, ...], "groups": [[block, ...], ...],
+    "runs": [[block, ...], ...], "segs": [[(src, dst, len), ...] per group]}.  A range outside
+    the data raises ValueError (the message names the range)."""
+    L = load()
+    ol = np.ascontiguousarray(np.asarray(orig_lens, dtype=np.uint32))
+    offs, lens = _ranges_arrays(ranges)
+    counts = np.zeros(4, dtype=np.uint64)
+    rc = L.kolm_range_plan(ol.ctypes.data, len(ol), offs.ctypes.data, lens.ctypes.data, len(ranges), group_limit,
+                           None, None, None, None, None, None, counts.ctypes.data)
+    if rc == -1:
+        raise ValueError(L.kolm_last_error().decode())
+    if rc != KOLM_ECAP:
+        check(rc)
+    ns, ng, nr, nseg = (int(x) for x in counts)
+    sel = np.zeros(max(ns, 1), dtype=np.uint32)
+    gfirst = np.zeros(ng + 1, dtype=np.uint32)
+    rfirst = np.zeros(nr + 1, dtype=np.uint32)
+    gseg = np.zeros(ng + 1, dtype=np.uint32)
+    segs = (RangeSeg * max(nseg, 1))()
+    check(L.kolm_range_plan(ol.ctypes.data, len(ol), offs.ctypes.data, lens.ctypes.data, len(ranges), group_limit,
+                            sel.ctypes.data, gfirst.ctypes.data, rfirst.ctypes.data, gseg.ctypes.data,
+                            ctypes.addressof(segs), counts.ctypes.data, counts.ctypes.data))
+    sel = [int(b) for b in sel[:ns]]
+    return {"sel": sel,
+            "groups": [sel[int(gfirst[g]):int(gfirst[g + 1])] for g in range(ng)],
+            "runs": [sel[int(rfirst[r]):int(rfirst[r + 1])] for r in range(nr)],
+            "segs": [[(segs[i].src, segs[i].dst, segs[i].len) for i in range(int(gseg[g]), int(gseg[g + 1]))]
+                     for g in range(ng)]}
+
+
+_last_read: dict = {}
+
+
+def last_read() -> dict:
+    """kolm_read_stats of the last reader call made through this binding."""
+    return dict(_last_read)
+
+
+def reader_open(container, ctx=None):
+    """kolm_reader_open on ctx (None: the default context).  Returns (handle, info dict with
+    mode, size_field, total_len, nblocks, payload_bytes, methods, orig_lens).  A malformed
+    container raises ValueError / struct.error as decompress does."""
+    ensure_init()
+    blob = bytes(container)
+    h = ctypes.c_void_p()
+    rc = load().kolm_reader_open(ctx, blob, len(blob), ctypes.byref(h))
+    if rc == KOLM_EFORMAT:
+        raise ValueError(load().kolm_last_error().decode())
+    if rc == KOLM_ERANGE:
+        import struct
+        raise struct.error(load().kolm_last_error().decode())
+    check(rc)
+    info = np.zeros(5, dtype=np.uint64)
+    check(load().kolm_reader_info(h, info.ctypes.data, None, None, 0))
+    nb = int(info[3])
+    meth = np.zeros(max(nb, 1), dtype=np.uint32)
+    lens = np.zeros(max(nb, 1), dtype=np.uint32)
+    check(load().kolm_reader_info(h, info.ctypes.data, meth.ctypes.data, lens.ctypes.data, max(nb, 1)))
+    return h, {"mode": int(info[0]), "size_field": int(info[1]), "total_len": int(info[2]), "nblocks": nb,
+               "payload_bytes": int(info[4]), "methods": [int(m) for m in meth[:nb]],
+               "orig_lens": [int(n) for n in lens[:nb]]}
+
+
+def reader_close(h):
+    check(load().kolm_reader_close(h))
+
+
+def _read_check(rc):
+    if rc == -1:  # KOLM_EARG: a range outside the data, or a selected block that does not decode
+        raise ValueError(load().kolm_last_error().decode())
+    check(rc)
+
+
+def reader_read(h, ranges) -> bytes:
+    """kolm_reader_read: the ranges' bytes packed back to back, as one bytes object."""
+    global _last_read
+    offs, lens = _ranges_arrays(ranges)
+    total = int(lens[:len(ranges)].sum()) if ranges else 0
+    out = _new_bytes(total)
+    st = ReadStats()
+    _read_check(load().kolm_reader_read(h, offs.ctypes.data, lens.ctypes.data, len(ranges),
+                                        ctypes.cast(ctypes.c_char_p(out), ctypes.c_void_p) if total else None,
+                                        total, ctypes.byref(st)))
+    _last_read = st.as_dict()
+    return out
+
+
+def reader_read_device(h, ranges, dptr: int, cap: int):
+    """kolm_reader_read_device: the packed bytes stay at the device address dptr (cap bytes)."""
+    global _last_read
+    offs, lens = _ranges_arrays(ranges)
+    st = ReadStats()
+    _read_check(load().kolm_reader_read_device(h, offs.ctypes.data, lens.ctypes.data, len(ranges), dptr, cap,
+                                               ctypes.byref(st)))
+    _last_read = st.as_dict()
