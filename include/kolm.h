@@ -22,6 +22,9 @@
  *                             equivalent: decompress, PY:2451-2550, decodes every block): only
  *                             the blocks a byte range touches are decoded, the ranges are packed
  *                             on the device (k_range.hip, kolm_range.cpp).
+ *   kolm_*_dedup* / kolm_dedup_plan: encode the repeated blocks of a batch once (PY has no
+ *                             equivalent: the loop at PY:2350-2369 encodes every block); opt-in,
+ *                             outputs byte-identical (k_dedup.hip, kolm_dedup.cpp).
  *   kolm_comm_* / kolm_gather_payloads: RCCL over xGMI (kolm_comm.cpp) — the reassembly
  *                             of independently encoded block shards (PY:2350-2369 blocks,
  *                             PY:2375-2445 the container they feed) onto one rank.
@@ -412,6 +415,80 @@ int kolm_reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens,
  * the ranges' bytes are written). */
 int kolm_reader_read_device(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges,
                             void* d_out, uint64_t out_cap, kolm_read_stats* stats);
+
+/* ---- dedup: encode repeated blocks once ---------------------------------------------- */
+/* A block's payload depends on its bytes, the candidate mask and its forced method and on
+ * nothing else (PY:2350-2369 loops over the blocks independently), so a batch can encode each
+ * distinct block once and copy that payload to every repeat: the outputs are byte for byte those
+ * of a call without dedup (the KOLR format cannot reference an earlier block: the saving is time,
+ * not bytes).  Default off, or KOLM_DEDUP=1 at context creation.  When enabled, every device
+ * batch of kolm_encode_blocks, kolm_encode_blocks_device, kolm_encode_blocks_device_var,
+ * kolm_compress_fixed (each piece on its own) and kolm_encode_blocks_multi (each shard on its
+ * own; the per-device contexts take the default context's setting) first fingerprints its blocks
+ * on the device (k_block_fp: one streaming read, 16 bytes per block come back), groups them on
+ * the host by (length, forced method, fingerprint), compares every group member with the group's
+ * lowest-numbered block byte for byte (k_dedup_cmp) and, when that confirms duplicates, packs the
+ * distinct blocks into a scratch text, encodes those into a scratch arena and copies every
+ * block's payload from its representative's into the caller's arena (k_range_gather).  Blocks
+ * with different forced methods are never duplicates of each other.  kolm_stats of such a call
+ * describes the work that ran: the distinct blocks.  Verify, when also on, checks the expanded
+ * arena against the original text: block numbers are container numbers.  Without a confirmed
+ * duplicate the original buffer is encoded exactly as with dedup off.  Disabled: no extra
+ * launch, allocation or synchronisation.
+ * With dedup on, up to 15 bytes on either side of d_data[0, total) may be read (and dropped) by
+ * the packing copy: they lie inside the aligned 16-byte word of a valid byte, hence inside any
+ * allocation that holds the data.  The fingerprint and compare kernels read [0, total) only.
+ * $KOLM_DEDUP_BITS=<0..128> (test switch, read per call, dedup on only) keeps that many low bits
+ * of the fingerprint for the grouping, so that the collision path runs. */
+typedef struct kolm_dedup_report {
+    uint32_t blocks;           /* blocks of the call's batches */
+    uint32_t blocks_encoded;   /* of which: distinct, encoded */
+    uint32_t candidate_pairs;  /* (block, representative) pairs compared byte for byte */
+    uint32_t collisions;       /* of which: different bytes under one fingerprint */
+    uint64_t bytes;            /* bytes of the batches */
+    uint64_t bytes_encoded;    /* bytes of the distinct blocks */
+    double ms_hash;            /* device time of k_block_fp (HIP events) */
+    double ms_compare;         /* of k_dedup_cmp */
+    double ms_compact;         /* of the gather that packs the distinct blocks */
+    double ms_expand;          /* of the gather that spreads the payloads */
+} kolm_dedup_report;
+int kolm_ctx_set_dedup(kolm_ctx* ctx, int enable);
+int kolm_set_dedup(int enable);  /* default context */
+/* The report accumulated over the batches of the last encode call of ctx (NULL: the default
+ * context); all zero when that call ran with dedup off. */
+int kolm_ctx_dedup_report(kolm_ctx* ctx, kolm_dedup_report* rep);
+/* The fingerprints of the blocks of d_data (device; block i = [h_bounds[i], h_bounds[i+1]),
+ * h_bounds[0] = 0, non-empty blocks, nblocks + 1 host entries, total < 2^31; any alignment):
+ * h_fp[2 i], h_fp[2 i + 1] = block i's 128 bits.  A function of the block's bytes alone; it may
+ * change between versions of the library and must not be persisted. */
+int kolm_block_fingerprints_device(kolm_ctx* ctx, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                                   uint64_t* h_fp);
+/* The confirmed duplicate map of the same blocks without encoding anything: h_rep[i] = i for a
+ * distinct block, else the lowest-numbered block with the same bytes that the plan paired it with
+ * (kolm_dedup_plan); *rep (optional) the counts and times. */
+int kolm_find_duplicates_device(kolm_ctx* ctx, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                                uint32_t* h_rep, kolm_dedup_report* rep);
+/* The host plan (no device call, usable without a GPU).  lens / fps (2 words per block) /
+ * force_method (optional; entries < 0 = not forced) describe nblocks blocks; fp_bits (0..128) =
+ * low fingerprint bits that count.
+ * Phase A: blocks are grouped by (length, forced id or -1, fingerprint); a group's representative
+ * is its lowest-numbered block; every other member gives a pair (member, representative):
+ * pairs[2 p], pairs[2 p + 1], ascending by member; counts[0] = the pairs.  With differ == NULL
+ * and at least one pair the call ends here (counts[1] = counts[2] = 0).
+ * Phase B (differ[p] != 0: pair p's blocks differ): rep[i] = i for distinct blocks and the
+ * representative for confirmed duplicates; a member that differs from its representative is
+ * encoded itself and is nobody's representative.  distinct = the blocks with rep[i] = i,
+ * ascending (counts[1] of them; counts[2] = the collisions); compact[q] = the copy of distinct
+ * block q from the batch (src) into the dense text (dst).  Given distinct_off (counts[1] + 1
+ * payload offsets of the distinct blocks): payload_off (nblocks + 1, a prefix sum in block order)
+ * and expand[i] = the copy of block i's payload from its representative's (src relative to
+ * distinct_off[0]) to payload_off[i].
+ * Every output array holds nblocks entries (pairs 2 * nblocks, payload_off nblocks + 1); each
+ * may be NULL (payload_off not when distinct_off is given). */
+int kolm_dedup_plan(const uint32_t* lens, const uint64_t* fps, const int32_t* force_method, uint32_t nblocks,
+                    uint32_t fp_bits, const uint32_t* differ, uint32_t* pairs, uint32_t* rep, uint32_t* distinct,
+                    kolm_range_seg* compact, const uint64_t* distinct_off, uint64_t* payload_off,
+                    kolm_range_seg* expand, uint32_t* counts);
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (kolm_comm.cpp) ------------- */
 /* The only data exchange of the multi-GPU path: blocks are independent (PY:2350-2369), so

@@ -27,6 +27,7 @@
 #include "../../include/kolm.h"
 #include "kolm_internal.h"
 #include "verify_core.h"
+#include "dedup_core.h"
 
 using namespace kolm;
 
@@ -177,6 +178,11 @@ struct kolm_ctx {
     bool verify = false;
     kolm_verify_report vrep{};
     u32 vshard = 0;
+    // dedup (kolm_ctx_set_dedup; KOLM_DEDUP=1): every encode batch encodes each distinct block
+    // once (encode_batch below); drep accumulates over the batches of one call
+    bool dedup = false;
+    kolm_dedup_report drep{};
+    hipEvent_t evd[2] = {};        // dedup: the event pair around its kernels
     // pinned host staging: an upload ring (input chunks) and the result buffer of
     // kolm_compress_fixed (container bytes, valid until the next call on this context)
     static constexpr int NSTAGE = 4;
@@ -1008,9 +1014,29 @@ int verify_encoded(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bo
                    const u64* off, const u32* win, hipEvent_t emitted, kolm_stats* stats);
 void verify_message(const kolm_verify_report& r);  // kolm_last_error text of a failed verify
 
+// What every encode entry point calls: encode_each, or with dedup on the distinct blocks through
+// it and their payloads spread over the repeats (defined with the gather's callers below).
 int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
                  const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
-                 kolm_stats* stats) {
+                 kolm_stats* stats);
+
+// the checks of a batch that depend on the candidate mask (N bytes, longest block bs)
+int check_mask(u32 mask, u64 N, u32 bs) {
+    if (((mask >> KOLM_M_V2NEW) & 1u) && 8 * N >= (1ull << 32)) {
+        set_err("v2_new (candidate 10): batches up to 512 MiB");
+        return KOLM_EARG;
+    }
+    if (((mask >> KOLM_M_REPAIR) & 1u) && bs > RP_MAX_N) {
+        set_err("Re-Pair (candidate 9) supports blocks up to 4 MiB (KOLM_REPAIR_MAX_BLOCK)");
+        return KOLM_EARG;
+    }
+    return KOLM_OK;
+}
+
+// every block of the batch encoded on its own
+int encode_each(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
+                const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
+                kolm_stats* stats) {
     Geom geo;
     if (h_bounds) {
         if (int e = check_bounds(h_bounds, nbv)) return e;
@@ -1030,14 +1056,7 @@ int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
         return KOLM_OK;
     }
     // every argument check before the first launch: an error return never leaves work in flight
-    if (((mask >> KOLM_M_V2NEW) & 1u) && 8 * N >= (1ull << 32)) {
-        set_err("v2_new (candidate 10): batches up to 512 MiB");
-        return KOLM_EARG;
-    }
-    if (((mask >> KOLM_M_REPAIR) & 1u) && bs > RP_MAX_N) {
-        set_err("Re-Pair (candidate 9) supports blocks up to 4 MiB (KOLM_REPAIR_MAX_BLOCK)");
-        return KOLM_EARG;
-    }
+    if (int e = check_mask(mask, N, bs)) return e;
     // Two streams: the index stream (main) runs the xor/lfsr size counters, the BBWT
     // predecessor bytes and the LZ77 parse (k_lz_local + stitch); the sort stream (aux,
     // higher priority: the critical path) runs the Lyndon factorisation, the cyclic sort,
@@ -1450,6 +1469,7 @@ int ctx_create(int device, kolm_ctx** out) {
         c->active = c->stream;
         c->serial = getenv("KOLM_SERIAL") && atoi(getenv("KOLM_SERIAL")) != 0;
         c->verify = getenv("KOLM_VERIFY") && atoi(getenv("KOLM_VERIFY")) != 0;
+        c->dedup = getenv("KOLM_DEDUP") && atoi(getenv("KOLM_DEDUP")) != 0;
         for (auto& e : c->evj) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evr) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evg) KOLM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1472,6 +1492,7 @@ kolm_ctx* need_default() {
 
 // start of an encode call (context lock held): the verify report covers this call's batches
 void verify_begin(kolm_ctx* c, u32 first_block = 0) {
+    c->drep = kolm_dedup_report{};  // the dedup report covers this call's batches too (zero when off)
     if (!c->verify) return;
     c->vrep = kolm_verify_report{};
     c->vshard = first_block;
@@ -1586,6 +1607,8 @@ int kolm_ctx_destroy(kolm_ctx* c) {
         for (auto& e : c->evr) KOLM_HIP_CHECK(hipEventDestroy(e));
         for (auto& e : c->evg) KOLM_HIP_CHECK(hipEventDestroy(e));
         KOLM_HIP_CHECK(hipEventDestroy(c->eva));
+        for (auto& e : c->evd)
+            if (e) KOLM_HIP_CHECK(hipEventDestroy(e));
         for (auto& e : c->evpool) KOLM_HIP_CHECK(hipEventDestroy(e));
         KOLM_HIP_CHECK(hipHostFree(c->h_cnt));
         if (c->h_rt) KOLM_HIP_CHECK(hipHostFree(c->h_rt));
@@ -2069,12 +2092,13 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
     // the shards' payloads stay in each device's arena until the reassembly below
     static const bool host_gather = getenv("KOLM_MULTI_GATHER") && !strcmp(getenv("KOLM_MULTI_GATHER"), "host");
     // verify: the per-device contexts take the default context's setting for this call
-    bool verify = false;
+    bool verify = false, dedup = false;  // dedup likewise: duplicates are found within a shard
     {
         std::lock_guard<std::mutex> g(g_mu);
         if (g_default) {
             std::lock_guard<std::mutex> gc(g_default->mu);
             verify = g_default->verify;
+            dedup = g_default->dedup;
         }
     }
     struct Part {
@@ -2082,6 +2106,7 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
         std::string err;
         bool checked = false;  // verify ran on this shard
         kolm_verify_report vrep{};
+        kolm_dedup_report drep{};
         const u8* d_pay = nullptr;
         std::vector<u64> off;
         kolm_stats st{};
@@ -2117,6 +2142,7 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
             u8* arena = c->get<u8>("arena", dcap);
             P.off.assign(nbr + 1, 0);
             c->verify = verify;
+            c->dedup = dedup;
             verify_begin(c, b0[r]);
             int rc = encode_batch(c, d, n, block_size, nullptr, 0, cand_mask & KOLM_FULL_MASK,
                                   force_method ? force_method + b0[r] : nullptr, arena, dcap,
@@ -2124,6 +2150,7 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
                                   P.off.data(), stats ? &P.st : nullptr);
             P.checked = verify;
             P.vrep = c->vrep;
+            P.drep = c->drep;
             if (rc && rc != KOLM_EVERIFY) return rc;  // a failed verify still hands out the payloads
             P.d_pay = arena;
             return KOLM_OK;
@@ -2217,6 +2244,28 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
             }
         }
         *stats = agg;
+    }
+    {
+        // the shards' dedup reports summed (times: the slowest shard), kept on the default context
+        kolm_dedup_report all{};
+        for (u32 r = 0; r < G; ++r) {
+            const kolm_dedup_report& d = part[r].drep;
+            all.blocks += d.blocks;
+            all.blocks_encoded += d.blocks_encoded;
+            all.candidate_pairs += d.candidate_pairs;
+            all.collisions += d.collisions;
+            all.bytes += d.bytes;
+            all.bytes_encoded += d.bytes_encoded;
+            all.ms_hash = std::max(all.ms_hash, d.ms_hash);
+            all.ms_compare = std::max(all.ms_compare, d.ms_compare);
+            all.ms_compact = std::max(all.ms_compact, d.ms_compact);
+            all.ms_expand = std::max(all.ms_expand, d.ms_expand);
+        }
+        std::lock_guard<std::mutex> g(g_mu);
+        if (g_default) {
+            std::lock_guard<std::mutex> gc(g_default->mu);
+            g_default->drep = all;
+        }
     }
     if (verify) {
         // the shards' reports (block numbers are the call's) in shard order, kept on the default context
@@ -2945,6 +2994,320 @@ void gather_segments(kolm_ctx* c, const char* name, const u8* src, u8* dst, cons
     KOLM_HIP_CHECK(hipEventRecord(e1, s));
 }
 
+// ---- dedup: encode repeated blocks once (dedup_core.h, k_dedup.hip, kolm_dedup.cpp) ----
+// What the detection finds in one batch.
+struct Dedup {
+    std::vector<u32> pairs, rep, distinct;
+};
+
+// the launches recorded by the dedup steps go to the per-kernel table only: kolm_stats describes
+// the encode of the distinct blocks
+void dedup_collect(kolm_ctx* c) {
+    if (c->timing) c->timing_collect_tail(0, nullptr);
+}
+
+// Fingerprints of the batch's blocks (fp: 2 words per block) by k_block_fp on c->stream: one
+// streaming read, one read-back of 16 bytes per block, the length mixed in on the host.
+void dedup_fingerprints(kolm_ctx* c, const u8* d_text, const Geom& geo, const std::vector<u32>& lens,
+                        std::vector<u64>& fp, kolm_dedup_report& rep) {
+    hipStream_t s = c->stream;
+    const u32 nb = geo.nb;
+    u64* dfp = c->get<u64>("dd_fp", 2 * (u64)nb);
+    KOLM_HIP_CHECK(hipMemsetAsync(dfp, 0, 2 * sizeof(u64) * nb, s));
+    const u32* dscan = nullptr;
+    u64 nruns = (u64)nb * ddp::runs(geo.bs);  // runs of up to ddp::RUN pieces
+    std::vector<u32> scan;
+    if (geo.bounds()) {  // variable geometry: the blocks' run counts differ
+        scan.assign((size_t)nb + 1, 0);
+        for (u32 b = 0; b < nb; ++b) scan[b + 1] = scan[b] + (u32)ddp::runs(lens[b]);  // < 2^17 + nb
+        u32* d = c->get<u32>("dd_scan", (size_t)nb + 1);
+        KOLM_HIP_CHECK(hipMemcpyAsync(d, scan.data(), sizeof(u32) * ((size_t)nb + 1), hipMemcpyHostToDevice, s));
+        dscan = d;
+        nruns = scan[nb];
+    }
+    KOLM_HIP_CHECK(hipEventRecord(c->evd[0], s));
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_block_fp", geo.N);
+        launch_block_fp(d_text, geo, dscan, nruns, dfp, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(c->evd[1], s));
+    fp.resize(2 * (size_t)nb);
+    KOLM_HIP_CHECK(hipMemcpyAsync(fp.data(), dfp, 2 * sizeof(u64) * nb, hipMemcpyDeviceToHost, s));
+    c->sync();
+    rep.ms_hash += ev_ms(c->evd[0], c->evd[1]);
+    for (u32 b = 0; b < nb; ++b) ddp::finish(fp[2 * (u64)b], fp[2 * (u64)b + 1], lens[b], &fp[2 * (u64)b]);
+}
+
+// differ[p] != 0: the blocks of pair p differ (k_dedup_cmp on c->stream, one read-back)
+void dedup_compare(kolm_ctx* c, const u8* d_text, const Geom& geo, const std::vector<u32>& lens,
+                   const std::vector<u32>& pairs, std::vector<u32>& differ, kolm_dedup_report& rep) {
+    hipStream_t s = c->stream;
+    const u32 np = (u32)(pairs.size() / 2);
+    std::vector<u32> scan((size_t)np + 1, 0);
+    u64 items = 0, bytes = 0;
+    for (u32 p = 0; p < np; ++p) {
+        items += ddp::pieces(lens[pairs[2 * p]]);
+        bytes += 2ull * lens[pairs[2 * p]];
+        if (items > 0xFFFFFFFFull) throw kolm::HipError(hipErrorInvalidValue, "more than 2^32 - 1 compare items", __LINE__);
+        scan[p + 1] = (u32)items;
+    }
+    u32* dpairs = c->get<u32>("dd_pairs", 2 * (size_t)np);
+    u32* dscan = c->get<u32>("dd_pscan", (size_t)np + 1);
+    u32* ddiff = c->get<u32>("dd_differ", np);
+    KOLM_HIP_CHECK(hipMemcpyAsync(dpairs, pairs.data(), sizeof(u32) * 2 * np, hipMemcpyHostToDevice, s));
+    KOLM_HIP_CHECK(hipMemcpyAsync(dscan, scan.data(), sizeof(u32) * ((size_t)np + 1), hipMemcpyHostToDevice, s));
+    KOLM_HIP_CHECK(hipMemsetAsync(ddiff, 0, sizeof(u32) * np, s));
+    KOLM_HIP_CHECK(hipEventRecord(c->evd[0], s));
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_dedup_cmp", bytes);
+        launch_dedup_cmp(d_text, geo, dpairs, dscan, np, items, ddiff, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(c->evd[1], s));
+    differ.resize(np);
+    KOLM_HIP_CHECK(hipMemcpyAsync(differ.data(), ddiff, sizeof(u32) * np, hipMemcpyDeviceToHost, s));
+    c->sync();
+    rep.ms_compare += ev_ms(c->evd[0], c->evd[1]);
+}
+
+// Steps 1-5 of a deduplicated batch: fingerprints, one read-back, plan A, the compare (only when
+// there are pairs) with its read-back, plan B.  rep gains blocks, pairs, collisions and bytes.
+// Context lock held, device set; synchronised on return.
+void dedup_find(kolm_ctx* c, const u8* d_text, const Geom& geo, const std::vector<u32>& lens, const int32_t* h_force,
+                Dedup& d, kolm_dedup_report& rep) {
+    for (auto& e : c->evd)
+        if (!e) KOLM_HIP_CHECK(hipEventCreate(&e));
+    c->active = c->stream;
+    c->timing_reset();
+    u32 bits = 128;
+    if (const char* e = getenv("KOLM_DEDUP_BITS")) bits = (u32)std::min<u64>(128, strtoull(e, nullptr, 10));  // test switch
+    std::vector<u64> fp;
+    dedup_fingerprints(c, d_text, geo, lens, fp, rep);
+    dedup_pairs(lens.data(), fp.data(), h_force, geo.nb, bits, d.pairs);
+    std::vector<u32> differ;
+    if (!d.pairs.empty()) dedup_compare(c, d_text, geo, lens, d.pairs, differ, rep);
+    const u32 coll = dedup_map(geo.nb, d.pairs, differ.data(), d.rep, d.distinct);
+    dedup_collect(c);
+    rep.blocks += geo.nb;
+    rep.candidate_pairs += (u32)(d.pairs.size() / 2);
+    rep.collisions += coll;
+    rep.bytes += geo.N;
+}
+
+int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
+                 const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
+                 kolm_stats* stats) {
+    if (!c->dedup)
+        return encode_each(c, d_text, N, bs, h_bounds, nbv, mask, h_force, d_arena, arena_cap, h_sizes, h_method, h_off,
+                           stats);
+    // every argument check of encode_each before the first launch
+    std::vector<u32> lens;
+    u32 longest = bs;
+    if (h_bounds) {
+        if (int e = check_bounds(h_bounds, nbv)) return e;
+        N = h_bounds[nbv];
+        lens.resize(nbv);
+        longest = 0;
+        for (u32 b = 0; b < nbv; ++b) longest = std::max(longest, lens[b] = h_bounds[b + 1] - h_bounds[b]);
+    } else {
+        if (int e = check_geom(N, bs)) return e;
+        lens.assign((size_t)((N + bs - 1) / bs), bs);
+        if (!lens.empty()) lens.back() = (u32)(N - (u64)(lens.size() - 1) * bs);
+    }
+    const u32 nb = (u32)lens.size();
+    if (nb == 0)
+        return encode_each(c, d_text, N, bs, h_bounds, nbv, mask, h_force, d_arena, arena_cap, h_sizes, h_method, h_off,
+                           stats);
+    if (int e = check_mask(mask, N, longest)) return e;
+    hipStream_t s = c->stream;  // the stream the callers order behind the text's upload
+    Geom geo;
+    if (h_bounds) {
+        const u32 vs = geom_var_shift(h_bounds, nb);
+        geom_init_var(geo, h_bounds, nb, c->get<u32>("dd_vb", (u64)nb + 1), c->get<u32>("dd_vmap", (N >> vs) + 2), vs, s);
+    } else {
+        geom_init(geo, N, bs);
+    }
+    Dedup d;
+    dedup_find(c, d_text, geo, lens, h_force, d, c->drep);
+    const u32 nd = (u32)d.distinct.size();
+    if (nd == nb) {  // no confirmed duplicate: the original buffer exactly as without dedup, no copy
+        c->drep.blocks_encoded += nb;
+        c->drep.bytes_encoded += N;
+        return encode_each(c, d_text, N, bs, h_bounds, nbv, mask, h_force, d_arena, arena_cap, h_sizes, h_method, h_off,
+                           stats);
+    }
+    // the distinct blocks packed into a dense scratch text (ours: 256-byte aligned, 64 zero bytes
+    // behind it as upload() leaves them); the gather reads the caller's text in aligned words
+    std::vector<rng::Seg> segs;
+    std::vector<u32> scan;
+    dedup_compact(lens.data(), nb, d.distinct, segs);
+    const u64 Nc = segs.back().dst + segs.back().len;
+    u8* ctext = c->get<u8>("dd_text", Nc + 64);
+    KOLM_HIP_CHECK(hipMemsetAsync(ctext + Nc, 0, 64, s));
+    gather_segments(c, "dd_c", d_text, ctext, segs.data(), nd, scan, c->evd[0], c->evd[1]);
+    c->sync();
+    c->drep.ms_compact += ev_ms(c->evd[0], c->evd[1]);
+    dedup_collect(c);
+    // A fixed-geometry batch stays fixed: its only block of another length is a short tail, which
+    // no other block can equal, so it is distinct and still last.  A content-defined batch stays
+    // variable, with the distinct blocks' bounds.
+    std::vector<u32> cb;
+    if (h_bounds) {
+        cb.assign((size_t)nd + 1, 0);
+        for (u32 q = 0; q < nd; ++q) cb[q + 1] = cb[q] + lens[d.distinct[q]];
+    }
+    std::vector<int32_t> cforce;
+    if (h_force)
+        for (u32 q = 0; q < nd; ++q) cforce.push_back(h_force[d.distinct[q]]);
+    const bool has_raw = (mask & 1u) && h_force == nullptr;  // sized as the callers size theirs
+    const u64 dcap = (has_raw ? Nc : 9 * Nc) + 64 * (u64)nd + 256;
+    u8* carena = c->get<u8>("dd_arena", dcap);
+    std::vector<u32> csizes(h_sizes ? (size_t)nd * KOLM_NCAND : 0), cmethod(nd);
+    std::vector<u64> coff((size_t)nd + 1);
+    {
+        // verify checks what is handed out: not the scratch arena here, the expanded one below
+        struct VerifyOff {
+            kolm_ctx* c;
+            bool was;
+            ~VerifyOff() { c->verify = was; }
+        } voff{c, c->verify};
+        c->verify = false;
+        if (int r = encode_each(c, ctext, Nc, bs, h_bounds ? cb.data() : nullptr, nd, mask, h_force ? cforce.data() : nullptr,
+                                carena, dcap, h_sizes ? csizes.data() : nullptr, cmethod.data(), coff.data(), stats))
+            return r;
+    }
+    // sizes, methods and offsets on the host; the payloads on the device into the caller's arena
+    std::vector<u64> off((size_t)nb + 1);
+    dedup_expand(d.rep, d.distinct, coff.data(), off.data(), segs);
+    if (off[nb] + 4 > arena_cap) {
+        set_err("payload arena too small");
+        return KOLM_ECAP;
+    }
+    c->active = s;
+    const size_t p0 = c->pend.size();
+    // the bytes behind the last payload that encode_each's emission leaves zero
+    KOLM_HIP_CHECK(hipMemsetAsync(d_arena + off[nb], 0, std::min<u64>((off[nb] + 8) & ~(u64)3, arena_cap) - off[nb], s));
+    gather_segments(c, "dd_x", carena, d_arena, segs.data(), nb, scan, c->evd[0], c->evd[1]);
+    c->sync();
+    c->drep.ms_expand += ev_ms(c->evd[0], c->evd[1]);
+    if (c->timing) c->timing_collect_tail(p0, nullptr);
+    c->drep.blocks_encoded += nd;
+    c->drep.bytes_encoded += Nc;
+    std::vector<u32> q(nb, 0), win(nb);
+    for (u32 j = 0; j < nd; ++j) q[d.distinct[j]] = j;
+    for (u32 i = 0; i < nb; ++i) {
+        const u32 j = q[d.rep[i]];
+        win[i] = cmethod[j];
+        if (h_sizes) std::memcpy(h_sizes + (size_t)i * KOLM_NCAND, csizes.data() + (size_t)j * KOLM_NCAND, sizeof(u32) * KOLM_NCAND);
+    }
+    if (h_method) std::memcpy(h_method, win.data(), sizeof(u32) * nb);
+    if (h_off) std::memcpy(h_off, off.data(), sizeof(u64) * ((size_t)nb + 1));
+    // block numbers are container numbers: the original text against the expanded arena, after
+    // the expansion (evd[1])
+    if (c->verify) return verify_encoded(c, d_text, N, bs, h_bounds, nb, d_arena, off.data(), win.data(), c->evd[1], stats);
+    return KOLM_OK;
+}
+
+// h_bounds (u64, as kolm_verify_blocks_device takes them) -> the variable geometry of the dedup
+// entry points: non-empty blocks, total < 2^31
+int dedup_geom(kolm_ctx* c, const uint64_t* h_bounds, u32 nb, std::vector<u32>& hb, std::vector<u32>& lens, Geom& geo) {
+    if (h_bounds[0] != 0) {
+        set_err("block bounds must start at 0");
+        return KOLM_EARG;
+    }
+    hb.assign((size_t)nb + 1, 0);
+    lens.resize(nb);
+    for (u32 b = 0; b < nb; ++b) {
+        if (h_bounds[b + 1] <= h_bounds[b] || h_bounds[b + 1] >= (1ull << 31)) {
+            set_err("blocks must be non-empty and contiguous, the batch smaller than 2^31 bytes");
+            return KOLM_EARG;
+        }
+        hb[b + 1] = (u32)h_bounds[b + 1];
+        lens[b] = hb[b + 1] - hb[b];
+    }
+    const u32 vs = geom_var_shift(hb.data(), nb);
+    geom_init_var(geo, hb.data(), nb, c->get<u32>("dd_vb", (u64)nb + 1), c->get<u32>("dd_vmap", ((u64)hb[nb] >> vs) + 2), vs,
+                  c->stream);
+    return KOLM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kolm_ctx_set_dedup(kolm_ctx* c, int enable) {
+    if (!c) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->dedup = enable != 0;
+    return KOLM_OK;
+}
+
+int kolm_set_dedup(int enable) {
+    kolm_ctx* c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    return kolm_ctx_set_dedup(c, enable);
+}
+
+int kolm_ctx_dedup_report(kolm_ctx* c, kolm_dedup_report* rep) {
+    if (!c) c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    if (!rep) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    *rep = c->drep;
+    return KOLM_OK;
+}
+
+int kolm_block_fingerprints_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                                   uint64_t* h_fp) {
+    if (!c) return KOLM_EARG;
+    if (nblocks == 0) return KOLM_OK;
+    if (!d_data || !h_bounds || !h_fp) return KOLM_EARG;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        std::vector<u32> hb, lens;
+        Geom geo;
+        if (int e = dedup_geom(c, h_bounds, nblocks, hb, lens, geo)) return e;
+        for (auto& e : c->evd)
+            if (!e) KOLM_HIP_CHECK(hipEventCreate(&e));
+        c->active = c->stream;
+        c->timing_reset();
+        std::vector<u64> fp;
+        kolm_dedup_report r{};
+        dedup_fingerprints(c, static_cast<const u8*>(d_data), geo, lens, fp, r);
+        dedup_collect(c);
+        std::memcpy(h_fp, fp.data(), sizeof(u64) * fp.size());
+        return KOLM_OK;
+    });
+}
+
+int kolm_find_duplicates_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                                uint32_t* h_rep, kolm_dedup_report* rep) {
+    if (!c) return KOLM_EARG;
+    kolm_dedup_report r{};
+    if (rep) *rep = r;
+    if (nblocks == 0) return KOLM_OK;
+    if (!d_data || !h_bounds || !h_rep) return KOLM_EARG;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        std::vector<u32> hb, lens;
+        Geom geo;
+        if (int e = dedup_geom(c, h_bounds, nblocks, hb, lens, geo)) return e;
+        Dedup d;
+        dedup_find(c, static_cast<const u8*>(d_data), geo, lens, nullptr, d, r);
+        r.blocks_encoded = (u32)d.distinct.size();
+        for (u32 b : d.distinct) r.bytes_encoded += lens[b];
+        std::memcpy(h_rep, d.rep.data(), sizeof(u32) * nblocks);
+        return KOLM_OK;
+    });
+    if (rep) *rep = r;
+    return rc;
+}
+
+}  // extern "C"
+
+namespace {
+
 // out (host) or d_out (device) receives the packed ranges.  Context lock not held on entry.
 int reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nr, uint8_t* out, void* d_out,
                 uint64_t out_cap, kolm_read_stats* stats) {
@@ -3251,8 +3614,9 @@ int kolm_bbwt_mtf_rice(const uint8_t* in, size_t n, int flags, int k, uint8_t* o
         const u64 dcap = 9 * n + 256;
         u8* arena = c->get<u8>("arena", dcap);
         std::vector<u64> off(2);
-        int r = encode_batch(c, d, n, (u32)n, nullptr, 0, 1u << force, &force, arena, dcap, nullptr, nullptr,
-                             off.data(), nullptr);
+        // one block: nothing to deduplicate, and no encode call whose dedup report this would join
+        int r = encode_each(c, d, n, (u32)n, nullptr, 0, 1u << force, &force, arena, dcap, nullptr, nullptr,
+                            off.data(), nullptr);
         if (r) return r;
         if (out_len) *out_len = off[1];
         if (off[1] > cap) {

@@ -652,6 +652,23 @@ u64 range_group_limit(u64 limit);  // 0: $KOLM_READ_BYTES or 1 GiB; capped at 2^
 // leaves [0, total_len].
 int range_plan(const u32* orig_lens, const u64* starts, u32 nblocks, const u64* offs, const u64* lens, u32 nranges,
                u64 limit, RangePlan& p);
+
+// ---- k_dedup.hip / kolm_dedup.cpp: duplicate-block detection (dedup_core.h) ----
+// fp [2 * nb] (zeroed by the caller on s) receives every block's two sums (ddp::finish on the host
+// turns them into the fingerprint).  scan: null when every block has ddp::runs(geo.bs) runs (fixed
+// geometry; nruns = nb * runs(bs)), else the device's exclusive scan of the per-block run counts
+// (nb + 1 words, nruns = scan[nb]).  Reads [text, text + geo.N) and nothing else.
+void launch_block_fp(const u8* text, const Geom& geo, const u32* scan, u64 nruns, u64* fp, hipStream_t s);
+// pairs [2 * npairs] block numbers of equal length (device), scan [npairs + 1] of their piece
+// counts; differ [npairs] (zeroed by the caller) gets 1 where a pair's blocks differ.  Same reads.
+void launch_dedup_cmp(const u8* text, const Geom& geo, const u32* pairs, const u32* scan, u32 npairs, u64 nitems,
+                      u32* differ, hipStream_t s);
+// the host plan (kolm_dedup_plan, include/kolm.h)
+void dedup_pairs(const u32* lens, const u64* fp, const int32_t* force, u32 nb, u32 bits, std::vector<u32>& pairs);
+u32 dedup_map(u32 nb, const std::vector<u32>& pairs, const u32* differ, std::vector<u32>& rep, std::vector<u32>& distinct);
+void dedup_compact(const u32* lens, u32 nb, const std::vector<u32>& distinct, std::vector<rng::Seg>& segs);
+void dedup_expand(const std::vector<u32>& rep, const std::vector<u32>& distinct, const u64* dist_off, u64* payload_off,
+                  std::vector<rng::Seg>& segs);
 }  // namespace kolm
 
 #define KOLM_HIP_CHECK(x)                                              \

@@ -49,7 +49,7 @@ __all__ = [
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
-    "open_container", "Reader", "last_read",
+    "open_container", "Reader", "last_read", "last_dedup", "duplicate_blocks", "block_fingerprints",
 ]
 
 CANDIDATE_NAMES = ["raw", "xor", "bbwt", "bbwt_bp", "bbwt_nib", "bbwt_br", "bbwt_gray", "lz77",
@@ -64,6 +64,9 @@ G_V2_NEW: bool = False
 # verify-after-encode (not in PY): every encode batch is decoded on the device and compared
 # with its input before the call returns; a bad block raises KolmVerifyError
 G_VERIFY: bool = False
+# dedup (not in PY): every device batch encodes its repeated blocks once and copies the payload
+# to the repeats; the output is byte for byte the same, the saving is time
+G_DEDUP: bool = False
 
 _last_stats: Dict[str, Any] = {}
 
@@ -81,6 +84,36 @@ def last_verify() -> Dict[str, Any]:
 
 def _want_verify(verify: Optional[bool]) -> bool:
     return G_VERIFY if verify is None else bool(verify)
+
+
+def last_dedup() -> Dict[str, Any]:
+    """Report of the last encode call when it ran with dedup on (kolm_dedup_report): blocks,
+    blocks_encoded, candidate_pairs, collisions, bytes, bytes_encoded, ms_hash, ms_compare,
+    ms_compact, ms_expand, summed over the call's device batches; empty when it ran with dedup off."""
+    return _lib.last_dedup()
+
+
+def _want_dedup(dedup: Optional[bool]) -> bool:
+    return G_DEDUP if dedup is None else bool(dedup)
+
+
+def duplicate_blocks(data: bytes, block_size: Optional[int] = None, bounds=None) -> List[int]:
+    """The duplicate map of data's blocks (fixed blocks of block_size, or bounds[i]..bounds[i+1]),
+    found on the device without encoding anything: rep[i] = i for a block that would be encoded,
+    else the lower-numbered block with the same bytes that the plan paired it with
+    (kolm_dedup_plan: the first block of its length and fingerprint).  Fingerprints propose the
+    candidates, a byte-for-byte compare settles them; with real fingerprints a duplicate's
+    representative is the earliest block with its bytes, while a block whose fingerprint
+    collides with a different block's ($KOLM_DEDUP_BITS makes that happen) is its own
+    representative even when an identical block came before it."""
+    rep, _ = _lib.duplicate_blocks(data, block_size, bounds)
+    return [int(r) for r in rep]
+
+
+def block_fingerprints(data: bytes, block_size: Optional[int] = None, bounds=None, data_offset: int = 0):
+    """The device's 128-bit fingerprints of data's blocks, u64[nb, 2] (for tests: the function
+    may change between versions and must not be persisted)."""
+    return _lib.block_fingerprints(data, block_size, bounds, data_offset=data_offset)
 
 
 # ---------------------------------------------------------------------------
@@ -289,11 +322,13 @@ def candidate_mask(hot_path: bool = False, v2_new: Optional[bool] = None) -> int
 # ---------------------------------------------------------------------------
 
 def encode_blocks(data: bytes, block_size: int, cand_mask: Optional[int] = None, devices: int = 1,
-                  hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None):
+                  hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None,
+                  dedup: Optional[bool] = None):
     """Batched device MDL over fixed blocks: (method_ids, orig_lens, payloads, sizes).
     devices > 1 shards the blocks over that many GPUs of this process.  `verify` (default
     G_VERIFY): the payloads are decoded and compared with the input on the device before the
-    call returns (KolmVerifyError otherwise)."""
+    call returns (KolmVerifyError otherwise).  `dedup` (default G_DEDUP): repeated blocks are
+    encoded once per device batch (same result; last_dedup())."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
     global _last_stats
@@ -303,22 +338,26 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: Optional[int] = None,
         return [], [], [], None
     if devices > 1:
         sizes, method, payloads, st = _lib.encode_blocks_multi(bytes(data), block_size, devices, mask,
-                                                               verify=_want_verify(verify))
+                                                               verify=_want_verify(verify), dedup=_want_dedup(dedup))
     else:
-        sizes, method, payloads, st = _lib.encode_blocks(bytes(data), block_size, mask, verify=_want_verify(verify))
+        sizes, method, payloads, st = _lib.encode_blocks(bytes(data), block_size, mask, verify=_want_verify(verify),
+                                                         dedup=_want_dedup(dedup))
     _last_stats = st
     orig = [min(block_size, n - i) for i in range(0, n, block_size)]
     return [int(m) for m in method], orig, payloads, sizes
 
 
 def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1, hot_path: bool = False,
-                          v2_new: Optional[bool] = None, verify: Optional[bool] = None) -> bytes:
+                          v2_new: Optional[bool] = None, verify: Optional[bool] = None,
+                          dedup: Optional[bool] = None) -> bytes:
     """Fixed-size chunking + per-block MDL selection + KOLR container (PY:2332-2445).
     `devices` (not in PY) spreads the blocks over that many GPUs of this process;
     `hot_path` (not in PY) restricts the candidates to ids 0..8; `v2_new` (default
     G_V2_NEW) adds candidate 10 (see the module docstring); `verify` (not in PY, default
     G_VERIFY) checks on the device that every payload decodes to its block before the
-    container is handed out (KolmVerifyError, and no container, otherwise; last_verify())."""
+    container is handed out (KolmVerifyError, and no container, otherwise; last_verify());
+    `dedup` (not in PY, default G_DEDUP) encodes the repeated blocks of every device batch once
+    and copies the payload to the repeats: the same container in less time (last_dedup())."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
     global _last_stats
@@ -328,22 +367,25 @@ def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1,
         raise struct.error("'H' format requires 0 <= number <= 65535")
     if devices > 1:
         mids, orig, payloads, _ = encode_blocks(data, block_size, devices=devices, hot_path=hot_path, v2_new=v2_new,
-                                                verify=verify)
+                                                verify=verify, dedup=dedup)
         return write_container(MODE_FIXED, block_size, n, mids, orig, payloads)
     if n == 0:
         return write_container(MODE_FIXED, block_size, 0, [], [], [])
     # one native call: staged upload, batched encode, TOC, payloads into the container
-    blob, st = _lib.compress_fixed(data, block_size, candidate_mask(hot_path, v2_new), verify=_want_verify(verify))
+    blob, st = _lib.compress_fixed(data, block_size, candidate_mask(hot_path, v2_new), verify=_want_verify(verify),
+                                   dedup=_want_dedup(dedup))
     _last_stats = st
     return blob
 
 
 def compress_blocks_cdc(data: bytes, min_size: int = 4096, avg_size: int = 8192, max_size: int = 16384,
-                        hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None) -> bytes:
+                        hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None,
+                        dedup: Optional[bool] = None) -> bytes:
     """FastCDC chunking + per-block MDL selection + KOLR container in CDC mode
     (PY:2213-2326): boundaries and every candidate on the GPU, one batched device call for
     all chunks (variable block geometry), the TOC on the host.  `hot_path` (not in PY)
-    restricts the candidates to ids 0..8; `verify` as in compress_blocks_fixed."""
+    restricts the candidates to ids 0..8; `verify` and `dedup` as in compress_blocks_fixed
+    (identical chunks are encoded once; this adds no shift resistance to the chunking)."""
     global _last_stats
     bounds = cdc_fast_boundaries_strict(data, min_size, avg_size, max_size)
     if len(bounds) > 0xFFFF:  # PY packs the block count as '<H' before encoding (PY:2222)
@@ -353,7 +395,7 @@ def compress_blocks_cdc(data: bytes, min_size: int = 4096, avg_size: int = 8192,
         return write_container(MODE_CDC, avg_size, 0, [], [], [])
     edges = [s for s, _ in bounds] + [n]
     _, method, payloads, st = _lib.encode_blocks_var(bytes(data), edges, candidate_mask(hot_path, v2_new),
-                                                     verify=_want_verify(verify))
+                                                     verify=_want_verify(verify), dedup=_want_dedup(dedup))
     _last_stats = st
     return write_container(MODE_CDC, avg_size, n, [int(m) for m in method], [e - s for s, e in bounds], payloads)
 

@@ -10,6 +10,7 @@ already-loaded runtime (same SONAME) — see ``kolm.parallel``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import sys
@@ -137,6 +138,24 @@ class RangeSeg(ctypes.Structure):
     _fields_ = [("src", ctypes.c_uint64), ("dst", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
+class DedupReport(ctypes.Structure):
+    _fields_ = [
+        ("blocks", ctypes.c_uint32),
+        ("blocks_encoded", ctypes.c_uint32),
+        ("candidate_pairs", ctypes.c_uint32),
+        ("collisions", ctypes.c_uint32),
+        ("bytes", ctypes.c_uint64),
+        ("bytes_encoded", ctypes.c_uint64),
+        ("ms_hash", ctypes.c_double),
+        ("ms_compare", ctypes.c_double),
+        ("ms_compact", ctypes.c_double),
+        ("ms_expand", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 _lock = threading.Lock()
 _result_lock = threading.Lock()  # kolm_compress_fixed's result buffer (see compress_fixed)
@@ -201,6 +220,12 @@ SIGNATURES = [
     ("kolm_reader_info", I32, [P, P, P, P, U32]),
     ("kolm_reader_read", I32, [P, P, P, U32, P, U64, ctypes.POINTER(ReadStats)]),
     ("kolm_reader_read_device", I32, [P, P, P, U32, P, U64, ctypes.POINTER(ReadStats)]),
+    ("kolm_ctx_set_dedup", I32, [P, I32]),
+    ("kolm_set_dedup", I32, [I32]),
+    ("kolm_ctx_dedup_report", I32, [P, ctypes.POINTER(DedupReport)]),
+    ("kolm_block_fingerprints_device", I32, [P, P, P, U32, P]),
+    ("kolm_find_duplicates_device", I32, [P, P, P, U32, P, ctypes.POINTER(DedupReport)]),
+    ("kolm_dedup_plan", I32, [P, P, P, U32, U32, P, P, P, P, P, P, P, P, P]),
 ]
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
@@ -311,6 +336,180 @@ def last_verify() -> dict:
     return dict(_last_verify)
 
 
+def dedup_report(ctx=None) -> dict:
+    """The dedup report of ctx's (None: the default context's) last encode call
+    (kolm_ctx_dedup_report): all zero when that call ran with dedup off."""
+    rep = DedupReport()
+    rc = load().kolm_ctx_dedup_report(ctx, ctypes.byref(rep))
+    if rc:
+        raise KolmError(rc, "kolm_ctx_dedup_report")
+    return rep.as_dict()
+
+
+_last_dedup: dict = {}
+_ENV_DEDUP = os.environ.get("KOLM_DEDUP", "0").strip() not in ("", "0")  # the contexts' own default
+
+
+class _dedup_scope:
+    """Runs one native encode call with dedup on, on ctx (None: the default context), as
+    _verify_scope does for verify: the switch is set before and goes back to what KOLM_DEDUP
+    gave the context afterwards, and the call's report is kept for last_dedup().  The caller
+    holds _result_lock (_encode_scope)."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+
+    def _set(self, on: int) -> int:
+        L = load()
+        return L.kolm_set_dedup(on) if self.ctx is None else L.kolm_ctx_set_dedup(self.ctx, on)
+
+    def __enter__(self):
+        check(self._set(1))
+        return self
+
+    def __exit__(self, et, ev, tb):
+        global _last_dedup
+        if et is None or isinstance(ev, KolmVerifyError):
+            _last_dedup = dedup_report(self.ctx)
+        self._set(1 if _ENV_DEDUP else 0)
+        return False
+
+
+@contextlib.contextmanager
+def _encode_scope(verify: bool, dedup: bool, locked: bool = False, ctx=None):
+    """The switches of one native encode call.  dedup false: _verify_scope alone, the path as
+    it was (last_dedup() then reports nothing).  dedup true: _result_lock is taken once for
+    both switches (it is not reentrant), unless the caller holds it (locked).  With KOLM_DEDUP
+    set in the environment the contexts deduplicate whatever the argument says, so the call is
+    treated as dedup true and last_dedup() reports it."""
+    global _last_dedup
+    dedup = bool(dedup) or _ENV_DEDUP
+    if not dedup:
+        _last_dedup = {}
+        with _verify_scope(verify, locked, ctx):
+            yield
+        return
+    if not locked:
+        _result_lock.acquire()
+    try:
+        with _dedup_scope(ctx), _verify_scope(verify, True, ctx):
+            yield
+    finally:
+        if not locked:
+            _result_lock.release()
+
+
+def last_dedup() -> dict:
+    """kolm_dedup_report of the last encode call made through this binding; empty when that
+    call ran with dedup off."""
+    return dict(_last_dedup)
+
+
+def _bounds_array(n: int, block_size, bounds):
+    """u64 block bounds [nb + 1] of n bytes in blocks of block_size, or the given bounds."""
+    if bounds is None:
+        if not block_size or block_size <= 0:
+            raise ValueError("give a positive block_size or bounds")
+        b = list(range(0, n, block_size)) + [n]
+    else:
+        b = [int(x) for x in bounds]
+        if b[0] != 0 or b[-1] != n or any(y <= x for x, y in zip(b, b[1:])):
+            raise ValueError("bounds must start at 0, increase strictly and end at len(data)")
+    return np.ascontiguousarray(np.asarray(b, dtype=np.uint64))
+
+
+def block_fingerprints_device(ctx, d_data: int, bounds):
+    """kolm_block_fingerprints_device: u64[nb, 2].  Not a format: may change between versions."""
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
+    nb = len(b) - 1
+    fp = np.zeros((max(nb, 1), 2), dtype=np.uint64)
+    check(load().kolm_block_fingerprints_device(ctx, d_data, b.ctypes.data, nb, fp.ctypes.data))
+    return fp[:nb]
+
+
+def find_duplicates_device(ctx, d_data: int, bounds):
+    """kolm_find_duplicates_device: (rep u32[nb], report dict)."""
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
+    nb = len(b) - 1
+    rep = np.zeros(max(nb, 1), dtype=np.uint32)
+    r = DedupReport()
+    check(load().kolm_find_duplicates_device(ctx, d_data, b.ctypes.data, nb, rep.ctypes.data, ctypes.byref(r)))
+    return rep[:nb], r.as_dict()
+
+
+def _on_device(data, data_offset: int, device, fn):
+    """fn(ctx, device address of data) with data uploaded data_offset (0..15) bytes into a buffer."""
+    dev = ensure_init() if device is None else device
+    ctx = device_ctx(dev)
+    data = bytes(data)
+    dd = DeviceBuffer(ctx, data_offset + len(data) + 64)
+    try:
+        dd.upload(data, data_offset)
+        return fn(ctx, dd.ptr + data_offset)
+    finally:
+        dd.free()
+
+
+def block_fingerprints(data, block_size=None, bounds=None, device: int = None, data_offset: int = 0):
+    """Uploads data and returns its blocks' fingerprints, u64[nb, 2] (block_fingerprints_device)."""
+    if len(data) == 0:
+        return np.zeros((0, 2), dtype=np.uint64)
+    b = _bounds_array(len(data), block_size, bounds)
+    return _on_device(data, data_offset, device, lambda ctx, p: block_fingerprints_device(ctx, p, b))
+
+
+def duplicate_blocks(data, block_size=None, bounds=None, device: int = None, data_offset: int = 0):
+    """Uploads data and returns (rep, report): rep[i] = i for a distinct block, else the
+    lowest-numbered block with the same bytes (find_duplicates_device)."""
+    if len(data) == 0:
+        return np.zeros(0, dtype=np.uint32), DedupReport().as_dict()
+    b = _bounds_array(len(data), block_size, bounds)
+    return _on_device(data, data_offset, device, lambda ctx, p: find_duplicates_device(ctx, p, b))
+
+
+def dedup_plan(lens, fps, force=None, fp_bits: int = 128, differ=None, distinct_off=None) -> dict:
+    """kolm_dedup_plan (host only, no device).  differ None: {"pairs": [(member, rep), ...]} and,
+    when there are no pairs, phase B's keys too.  Otherwise also "rep", "distinct",
+    "collisions", "compact" [(src, dst, len)] and, given distinct_off (a function of the
+    distinct block list -> their payload offsets, or None), "payload_off" and "expand"."""
+    L = load()
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint32))
+    nb = len(ln)
+    fp = np.ascontiguousarray(np.asarray(fps, dtype=np.uint64).reshape(-1))
+    if fp.size != 2 * nb:
+        raise ValueError("fps must hold two words per block")
+    fz = None if force is None else np.ascontiguousarray(np.asarray(force, dtype=np.int32))
+    pairs = np.zeros(max(2 * nb, 1), dtype=np.uint32)
+    counts = np.zeros(3, dtype=np.uint32)
+    args = (ln.ctypes.data, fp.ctypes.data, fz.ctypes.data if fz is not None else None, nb, fp_bits)
+    check(L.kolm_dedup_plan(*args, None, pairs.ctypes.data, None, None, None, None, None, None, counts.ctypes.data))
+    npairs = int(counts[0])
+    out = {"pairs": [(int(pairs[2 * p]), int(pairs[2 * p + 1])) for p in range(npairs)]}
+    if differ is None and npairs:
+        return out
+    df = np.ascontiguousarray(np.asarray(differ if differ is not None else [], dtype=np.uint32))
+    if df.size != npairs:
+        raise ValueError("differ must hold one word per pair")
+    rep = np.zeros(max(nb, 1), dtype=np.uint32)
+    dist = np.zeros(max(nb, 1), dtype=np.uint32)
+    comp = (RangeSeg * max(nb, 1))()
+    check(L.kolm_dedup_plan(*args, df.ctypes.data if npairs else None, pairs.ctypes.data, rep.ctypes.data,
+                            dist.ctypes.data, ctypes.addressof(comp), None, None, None, counts.ctypes.data))
+    nd = int(counts[1])
+    out.update(rep=[int(x) for x in rep[:nb]], distinct=[int(x) for x in dist[:nd]], collisions=int(counts[2]),
+               compact=[(comp[i].src, comp[i].dst, comp[i].len) for i in range(nd)])
+    if distinct_off is not None:
+        doff = np.ascontiguousarray(np.asarray(distinct_off(out["distinct"]), dtype=np.uint64))
+        if doff.size != nd + 1:
+            raise ValueError("distinct_off must give one offset more than distinct blocks")
+        poff = np.zeros(nb + 1, dtype=np.uint64)
+        exp = (RangeSeg * max(nb, 1))()
+        check(L.kolm_dedup_plan(*args, df.ctypes.data if npairs else None, None, None, None, None, doff.ctypes.data,
+                                poff.ctypes.data, ctypes.addressof(exp), counts.ctypes.data))
+        out.update(payload_off=[int(x) for x in poff], expand=[(exp[i].src, exp[i].dst, exp[i].len) for i in range(nb)])
+    return out
+
+
 def verify_blocks_device(ctx, d_data: int, bounds, d_payloads: int, payload_off, methods):
     """kolm_verify_blocks_device: original and payloads device-resident.  Returns (first_bad
     u32[nb]: offset of the block's first differing byte, KOLM_VERIFY_EQUAL or
@@ -406,16 +605,17 @@ def device_ctx(device: int):
 
 
 def encode_blocks_device(ctx, d_data: int, n: int, block_size: int, d_arena: int, arena_cap: int,
-                         cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False):
+                         cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False, dedup: bool = False):
     """Batched MDL encode of fixed blocks of the device buffer d_data[0, n) into the
     device arena (kolm_encode_blocks_device).  Returns (sizes, method, offsets, stats).
-    verify: the batch is checked on ctx before the call returns (KolmVerifyError)."""
+    verify: the batch is checked on ctx before the call returns (KolmVerifyError).
+    dedup: repeated blocks are encoded once (same outputs; last_dedup())."""
     nb = (n + block_size - 1) // block_size if n else 0
     sizes = np.zeros((max(nb, 1), KOLM_NCAND), dtype=np.uint32)
     method = np.zeros(max(nb, 1), dtype=np.uint32)
     off = np.zeros(nb + 1, dtype=np.uint64)
     st = Stats()
-    with _verify_scope(verify, ctx=ctx):
+    with _encode_scope(verify, dedup, ctx=ctx):
         check(load().kolm_encode_blocks_device(ctx, d_data, n, block_size, cand_mask, None, d_arena, arena_cap,
                                                sizes.ctypes.data, method.ctypes.data, off.ctypes.data,
                                                ctypes.byref(st)), ctx)
@@ -549,10 +749,10 @@ def bbwt_mtf_rice(data: bytes, flags: int, k: int = 2) -> bytes:
 
 
 def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, force=None,
-                  verify: bool = False):
+                  verify: bool = False, dedup: bool = False):
     """Batched MDL encode of fixed-size blocks.  Returns (sizes[nb,KOLM_NCAND], method[nb],
     payloads list, stats dict).  verify: check the payloads on the device before returning
-    (KolmVerifyError on a bad block)."""
+    (KolmVerifyError on a bad block).  dedup: repeated blocks are encoded once."""
     ensure_init()
     n = len(data)
     nb = (n + block_size - 1) // block_size if n else 0
@@ -571,7 +771,7 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MA
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    with _verify_scope(verify):
+    with _encode_scope(verify, dedup):
         check(load().kolm_encode_blocks(
             data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
             fz.ctypes.data if fz is not None else None,
@@ -581,10 +781,11 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MA
     return sizes[:nb], method[:nb], payloads, st.as_dict()
 
 
-def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False):
+def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False,
+                   dedup: bool = False):
     """The whole KOLR container of data in fixed blocks (kolm_compress_fixed): (bytes, stats).
     verify: every device batch is checked before its payloads count (KolmVerifyError, no
-    container, on a bad block)."""
+    container, on a bad block).  dedup: every device batch encodes its repeated blocks once."""
     ensure_init()
     n = len(data)
     src = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8) if n else np.zeros(1, np.uint8)
@@ -595,7 +796,7 @@ def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, ve
     # copy out of it run under one lock (ctypes drops the GIL inside the call)
     with _result_lock:
         tc = time.perf_counter() if _HOST_PROF else 0.0
-        with _verify_scope(verify, locked=True):
+        with _encode_scope(verify, dedup, locked=True):
             rc = load().kolm_compress_fixed(src.ctypes.data, n, block_size, cand_mask, ctypes.byref(out),
                                             ctypes.byref(ln), ctypes.byref(st))
             if rc == KOLM_EVERIFY:
@@ -632,7 +833,8 @@ def _new_bytes(n: int) -> bytes:
     return _PyBytes_New(None, n) if n else b""
 
 
-def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, force=None, verify: bool = False):
+def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, force=None, verify: bool = False,
+                      dedup: bool = False):
     """Batched MDL encode of content-defined blocks: block i = data[bounds[i]:bounds[i+1]]
     (bounds[0] = 0, strictly increasing, bounds[-1] = len(data)).  Same return value as
     encode_blocks."""
@@ -655,7 +857,7 @@ def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, f
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    with _verify_scope(verify):
+    with _encode_scope(verify, dedup):
         check(load().kolm_encode_blocks(
             data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
             fz.ctypes.data if fz is not None else None,
@@ -678,7 +880,7 @@ def cdc_boundaries(data: bytes, min_size: int, avg_size: int, max_size: int, mer
 
 
 def encode_blocks_multi(data: bytes, block_size: int, ngpu: int, cand_mask: int = KOLM_DEFAULT_MASK,
-                        verify: bool = False):
+                        verify: bool = False, dedup: bool = False):
     """encode_blocks over ngpu devices of this process (contiguous block shards, one host
     thread per device; kolm_encode_blocks_multi).  Same return value."""
     ensure_init()
@@ -690,7 +892,7 @@ def encode_blocks_multi(data: bytes, block_size: int, ngpu: int, cand_mask: int 
     cap = 9 * n + 64 * nb + 64
     arena = np.zeros(cap, dtype=np.uint8)
     st = Stats()
-    with _verify_scope(verify):
+    with _encode_scope(verify, dedup):
         check(load().kolm_encode_blocks_multi(
             int(ngpu), data, n, block_size, cand_mask, None, sizes.ctypes.data, method.ctypes.data,
             arena.ctypes.data, cap, off.ctypes.data, ctypes.byref(st)))
