@@ -1,27 +1,31 @@
 // Suffix sorting for the BBWT (gfx950): segmented prefix doubling over a batch of blocks.
 //
 // Replaces the reference's per-factor comparison-sort prefix doubling + k-way heap merge
-// (PY:351-423, CPP:939-1093).  Two passes use these kernels:
-//   * linear  — suffix order of each block (sentinel < every byte), used for the Lyndon
-//               factorisation (factor starts = left-to-right minima of the inverse SA,
-//               replacing Duval PY:326-349) and for the LZ77 3-gram chains;
-//   * cyclic  — omega-order of all rotations of all Lyndon factors of a block
-//               (succ(p) = next position inside p's factor, cyclically).  A stable sort
-//               of positions by that order with ties in position order IS the BBWT
-//               order of PY's heap merge (ties (fi, i) = position order, PY:408-409).
+// (PY:351-423, CPP:939-1093).  sort_pass (kolm_api.cpp) runs one pass with these kernels, the
+// cyclic one (it is only ever called with cyclic = true; the kernels' linear branches - suffix
+// order with a sentinel, 3 packed characters in round 0 - have no caller):
+//   omega-order of all rotations of all Lyndon factors of a block (succ(p) = next position
+//   inside p's factor, cyclically).  A stable sort of positions by that order with ties in
+//   position order IS the BBWT order of PY's heap merge (ties (fi, i) = position order,
+//   PY:408-409).  The Lyndon factors come from the Duval kernels of k_blocks.hip.
 //
 // State per position: SA (positions in current order), RK (rank = SA index of the start
 // of the position's group), K2 (sort key of the current round, per SA slot).  Each round
 // refines every unsorted group ("segment") by the key of this round:
-//   round 0:  packed leading characters (linear: 3 x 9-bit chars with 0 = end;
-//             cyclic: 4 chars of the rotation)
+//   round 0:  the LSD pass of k_lsd.hip (launch_round0), not these kernels: a stable sort of
+//             every block's positions by the packed codes of the rotation's first C
+//             characters - 64-bit keys from the blocks' order-preserving prefix codes (8 or
+//             more whole characters, h0 = 8), or fixed-width alphabet-compacted codes
+//             (C = 64 / width, 8 for an 8-bit alphabet);
 //   round r:  RK[succ^h(p)] with h = h0 * 2^(r-1)  (prefix doubling).
-// Segments are processed by size: len <= TILE in one workgroup (LDS bitonic sort of
-// (key, position), which yields position order among equal keys), longer ones by stable
-// 8-bit MSD radix passes (LDS histograms, per-segment tile scan, stable scatter) until
-// their buckets fit a tile.  A group splitting or not is tracked per block: in cyclic
-// mode a block whose groups did not split in a doubling round can never split again
-// (E_2h == E_h => fixed point) and is retired.  See DESIGN.md §4.
+// Segments are processed by size: 2..16 elements by one thread each (k_tiny_sort), up to TILE
+// in one workgroup (LDS bitonic sort of (key, position), which yields position order among
+// equal keys), up to MED_T by one 1024-thread workgroup in batches of few blocks (k_med_sort),
+// longer ones by stable 8-bit MSD radix passes (LDS histograms, per-segment tile scan, stable
+// scatter) until their buckets fit a tile; a bucket still longer after the last digit is a run
+// of equal keys (k_finalize_eq).  A group splitting or not is tracked per block: a block whose
+// groups did not split in a doubling round can never split again (E_2h == E_h => fixed point)
+// and is retired.  See DESIGN.md §4 (the route matrix lists the tests that reach each route).
 #include "kolm_internal.h"
 
 namespace kolm {
