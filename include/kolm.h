@@ -457,6 +457,13 @@ int kolm_set_dedup(int enable);  /* default context */
 /* The report accumulated over the batches of the last encode call of ctx (NULL: the default
  * context); all zero when that call ran with dedup off. */
 int kolm_ctx_dedup_report(kolm_ctx* ctx, kolm_dedup_report* rep);
+/* Lyndon factorisation routes of the last batch ctx (NULL: the default context) factorised: the
+ * blocks whose factor starts came from the prefix-minimum candidates (accepted) and the blocks
+ * left to the parallel Duval kernels (fallback: periodic data that exceeds the candidate or
+ * common-prefix budget, or every block with $KOLM_LYN_FAST=0).  Both routes give the same factors.
+ * $KOLM_LYN_FAST=<0|1> (default 1), $KOLM_LYN_CAND_MAX=<1..1024> and $KOLM_LYN_LCP_MAX=<0..65536>
+ * (test switches that move the budgets) are read per call.  Waits for the batch. */
+int kolm_ctx_lyndon_report(kolm_ctx* ctx, uint32_t* accepted, uint32_t* fallback);
 /* The fingerprints of the blocks of d_data (device; block i = [h_bounds[i], h_bounds[i+1]),
  * h_bounds[0] = 0, non-empty blocks, nblocks + 1 host entries, total < 2^31; any alignment):
  * h_fp[2 i], h_fp[2 i + 1] = block i's 128 bits.  A function of the block's bytes alone; it may

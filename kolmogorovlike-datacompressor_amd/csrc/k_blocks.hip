@@ -4,9 +4,18 @@
 // Lyndon factor of its block iff its suffix is smaller than every suffix starting
 // before it inside the block, i.e. ISA[p] < min(ISA[base..p)) — left-to-right minima of
 // the inverse suffix array (the factors are the non-increasing Lyndon words, and the
-// last factor is the minimal suffix).  Computed as a tiled per-block prefix-min scan.
-// Then every position gets its factor's start FS and length FL (prefix-max of starts,
-// suffix-min of the next start).
+// last factor is the minimal suffix).  No suffix array exists at this point, so
+// launch_lyndon finds the starts from the text in two routes with one result:
+//   fast route (lyndon_core.h, k_lyn_*): a start's 8-byte big-endian word is <= the word
+//     of every earlier position of its block, so one streaming prefix-min pass leaves a
+//     few hundred candidates per text block; their left-to-right minima in suffix order
+//     (a parallel min-scan with short text comparisons) are the starts.  A block with
+//     more candidates or longer common prefixes than the budgets (periodic data) is
+//     left untouched, its route word says so;
+//   Duval route (k_duval_span / k_duval_merge): parallel Duval over every byte, for the
+//     blocks the fast route left (all of them with KOLM_LYN_FAST=0).
+// Both write the flags and the sorted start lists (Factors); k_tile_starts / k_fed then
+// give every position its distance to its factor's end (FEd).
 //
 // BBWT gather (PY:417: out.append(w[(i - 1) % m])): out[r] = text[prev(SA[r])] where
 // prev steps back cyclically inside the factor.
@@ -15,6 +24,7 @@
 #include <cstdlib>
 
 #include "kolm_internal.h"
+#include "lyndon_core.h"
 
 namespace kolm {
 
@@ -284,8 +294,10 @@ __device__ inline void dprof(u64* prof, u32 k, u64& last) {
 // or 256 (32 KiB)
 template <u32 NT>
 __global__ __launch_bounds__(NT) void k_duval_span(Geom geo, u32 spb, const u8* s, u32* fstart, uint4* fpre,
-                                                   u32* nfac, u64* prof, u32 wave_w, u32 grp) {
+                                                   u32* nfac, u64* prof, u32 wave_w, u32 grp, const u32* route) {
     constexpr u32 SPAN = DUVAL_CH * NT;
+    // the fast route resolved this span's block (workgroup-uniform, before the first barrier)
+    if (route && route[blockIdx.x / spb] == lyn::ACCEPT) return;
     u64 tlast = prof ? wall_clock64() : 0;
     __shared__ __align__(16) u8 t[SPAN + NT * DUVAL_PAD + 16];  // + 16: lds_word's reads past the end
     __shared__ u32 bm[SPAN / 32];
@@ -657,7 +669,8 @@ __device__ inline Pre rdl(const Pre& p, u32 l) {
 // comparisons per 1 MiB text block cost ~0.7 us of load latency each.
 __global__ __launch_bounds__(64) void k_duval_merge(Geom geo, u32 cpb, u32 span, const u8* s, const u32* fstart,
                                                     const uint4* fpre, const u32* nfac, u32* stack, u32* fcount,
-                                                    u8* flag, u64* prof) {
+                                                    u8* flag, u64* prof, const u32* route) {
+    if (route && route[blockIdx.x] == lyn::ACCEPT) return;  // resolved by the fast route
     __shared__ u32 lstk[MERGE_LDS];
     __shared__ Pre lpre[PRE_LDS];
     __shared__ u32 lok[PRE_LDS];
@@ -1045,6 +1058,231 @@ void launch_bbwt_gather_masked(const Geom& geo, const u32* SA, const u8* prevc, 
     k_bbwt_gather_m<<<(u32)((geo.N + 4095) / 4096), 256, 0, s>>>(geo, SA, prevc, out, bm);
 }
 
+// ---------------------------------------------------------------------------------
+// Fast route (lyndon_core.h): factor starts from prefix-minimum candidates.  Four launches
+// ordered by their kernel boundaries; a block's route word says whether it was resolved
+// here (ACCEPT) or is left, untouched, to the Duval kernels (FALLBACK).
+//   k_lyn_min      per 4 KiB tile of a block: the minimum word (one streaming read of the text)
+//   k_lyn_scan     per block: exclusive prefix-min of its tile minima; clears the route word
+//                  and the candidate count
+//   k_lyn_cand     tiles whose minimum is above the minimum entering them exit at once; a live
+//                  tile appends its candidates to the block's list (one atomic per tile; the
+//                  list's order is arbitrary); more than cap candidates: FALLBACK
+//   k_lyn_resolve  per block: rank sort by position, inclusive min-scan in suffix order,
+//                  compaction -> lyn_stack / lyn_fcount / flag.  A comparison past the LCP cap:
+//                  FALLBACK, nothing written
+// ---------------------------------------------------------------------------------
+namespace {
+
+struct LynReader {
+    const u8* t;
+    __device__ inline u32 amod() const { return (u32)((uintptr_t)t & 15u); }
+    __device__ inline u32 b(u32 i) const { return t[i]; }
+    __device__ inline u32 d(u32 i) const { return *reinterpret_cast<const u32*>(t + i); }
+    __device__ inline void q(u32 i, u32 e[4]) const {
+        const uint4 v = *reinterpret_cast<const uint4*>(t + i);
+        e[0] = v.x;
+        e[1] = v.y;
+        e[2] = v.z;
+        e[3] = v.w;
+    }
+};
+
+static_assert(lyn::THREADS == WG, "one lane per 16 positions of a 4 KiB tile");
+
+// the lane's 16 positions of tile t: p, n (0: none), and the block
+__device__ inline void lyn_lane(const Geom& geo, u32 tpb, u32 t, u32& b, u32& base, u32& end, u32& p, u32& n) {
+    b = t / tpb;
+    const u32 k = t - b * tpb;
+    base = geo.base(b);
+    end = geo.end(b);
+    const u64 p64 = (u64)base + (u64)k * lyn::TILE + threadIdx.x * lyn::PER;
+    p = p64 < end ? (u32)p64 : end;
+    n = min(lyn::PER, end - p);
+}
+
+__device__ inline u64 wave_min64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = lyn::min64(v, (u64)__shfl_xor((unsigned long long)v, o));
+    return v;
+}
+
+// inclusive prefix-min over the workgroup's 256 values (Hillis-Steele in LDS); sh[2][WG]
+__device__ inline u32 wg_scan_min64(u64 v, u64 (*sh)[WG]) {
+    const u32 tid = threadIdx.x;
+    u32 cur = 0;
+    sh[0][tid] = v;
+    __syncthreads();
+    for (u32 d = 1; d < WG; d <<= 1) {
+        u64 x = sh[cur][tid];
+        if (tid >= d) x = lyn::min64(x, sh[cur][tid - d]);
+        sh[cur ^ 1][tid] = x;
+        __syncthreads();
+        cur ^= 1;
+    }
+    return cur;  // the buffer that holds the result
+}
+
+__global__ __launch_bounds__(WG) void k_lyn_min(Geom geo, u32 tpb, const u8* text, u64* tmin) {
+    __shared__ u64 sh[WG / 64];
+    u32 b, base, end, p, n;
+    lyn_lane(geo, tpb, blockIdx.x, b, base, end, p, n);
+    u64 m = lyn::W_MAX;
+    if (n) {
+        u32 E[6];
+        lyn::load24(LynReader{text}, p, base, end, E);
+        m = lyn::lane_min(E, n);
+    }
+    m = wave_min64(m);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) tmin[blockIdx.x] = lyn::min64(lyn::min64(sh[0], sh[1]), lyn::min64(sh[2], sh[3]));
+}
+
+__global__ __launch_bounds__(WG) void k_lyn_scan(const u64* tmin, u64* tin, u32 tpb, u32* route, u32* ccount) {
+    __shared__ u64 sh[2][WG];
+    const u32 b = blockIdx.x, tid = threadIdx.x;
+    u64 carry = lyn::W_MAX;
+    for (u32 c0 = 0; c0 < tpb; c0 += WG) {
+        const u32 k = c0 + tid;
+        const u64 v = k < tpb ? tmin[(u64)b * tpb + k] : lyn::W_MAX;
+        const u32 cur = wg_scan_min64(v, sh);
+        const u64 ex = tid ? sh[cur][tid - 1] : lyn::W_MAX;
+        if (k < tpb) tin[(u64)b * tpb + k] = lyn::min64(carry, ex);
+        carry = lyn::min64(carry, sh[cur][WG - 1]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        route[b] = lyn::ACCEPT;
+        ccount[b] = 0;
+    }
+}
+
+__global__ __launch_bounds__(WG) void k_lyn_cand(Geom geo, u32 tpb, const u8* text, const u64* tmin, const u64* tin,
+                                                 u32 cap, u32* route, u32* ccount, u32* cand) {
+    __shared__ u64 sh[2][WG];
+    __shared__ u32 wsum[WG / 64];
+    __shared__ u32 gbase;
+    const u32 t = blockIdx.x, tid = threadIdx.x;
+    const u64 in = tin[t];
+    if (tmin[t] > in) return;  // no position of the tile can be a candidate (workgroup-uniform)
+    u32 b, base, end, p, n;
+    lyn_lane(geo, tpb, t, b, base, end, p, n);
+    u32 E[6] = {0, 0, 0, 0, 0, 0};
+    u64 m = lyn::W_MAX;
+    if (n) {
+        lyn::load24(LynReader{text}, p, base, end, E);
+        m = lyn::lane_min(E, n);
+    }
+    const u32 cur = wg_scan_min64(m, sh);
+    const u64 run = lyn::min64(in, tid ? sh[cur][tid - 1] : lyn::W_MAX);
+    const u32 mask = n ? lyn::lane_cands(E, n, run) : 0u;
+    const u32 cnt = (u32)__popc(mask);
+    const u32 incl = wave_incl_scan(cnt, OpAddU(), 0u);
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    u32 off = incl - cnt, total = 0;
+    for (u32 w = 0; w < WG / 64; ++w) {
+        if (w < (tid >> 6)) off += wsum[w];
+        total += wsum[w];
+    }
+    if (total == 0) return;  // uniform
+    if (tid == 0) {
+        const u32 g = atomicAdd(&ccount[b], total);
+        if (g + total > cap) atomicExch(&route[b], lyn::FALLBACK);
+        gbase = g;
+    }
+    __syncthreads();
+    u32 idx = gbase + off;
+    // the list lives in the block's own range of `cand`: idx < candidates of the block <= its length
+    for (u32 i = 0; i < lyn::PER; ++i)
+        if (mask >> i & 1) {
+            if (idx < cap) cand[base + idx] = p + i;
+            ++idx;
+        }
+}
+
+__global__ __launch_bounds__(WG) void k_lyn_resolve(Geom geo, const u8* text, u32 cap, u32 lcp_cap, u32* route,
+                                                    const u32* ccount, const u32* cand, u32* stack, u32* fcount,
+                                                    u8* flag) {
+    __shared__ u32 S[lyn::CAND_MAX], A[lyn::CAND_MAX], B[lyn::CAND_MAX];
+    __shared__ u32 wsum[WG / 64];
+    __shared__ u32 fb;
+    const u32 b = blockIdx.x, tid = threadIdx.x;
+    const u32 n = ccount[b];
+    if (n > cap || route[b] != lyn::ACCEPT) {  // workgroup-uniform
+        if (tid == 0) route[b] = lyn::FALLBACK;
+        return;
+    }
+    const u32 base = geo.base(b), end = geo.end(b);
+    const LynReader rd{text};
+    for (u32 i = tid; i < n; i += WG) A[i] = cand[base + i];
+    if (tid == 0) fb = 0;
+    __syncthreads();
+    for (u32 i = tid; i < n; i += WG) {  // rank sort by position (positions are distinct)
+        const u32 v = A[i];
+        u32 r = 0;
+        for (u32 j = 0; j < n; ++j) r += A[j] < v;
+        S[r] = v;
+        B[r] = v;
+    }
+    __syncthreads();
+    u32* in = B;
+    u32* out = A;
+    for (u32 d = 1; d < n; d <<= 1) {
+        for (u32 i = tid; i < n; i += WG) {
+            u32 lcp;
+            bool over;
+            out[i] = lyn::scan_step(rd, in, i, d, base, end, lcp_cap, lcp, over);
+            if (over) fb = 1;
+        }
+        __syncthreads();
+        u32* x = in;
+        in = out;
+        out = x;
+    }
+    if (fb) {  // read after the loop's last barrier (n = 1: after the sort's): uniform
+        if (tid == 0) route[b] = lyn::FALLBACK;
+        return;
+    }
+    // starts = candidates that are their own prefix minimum; four consecutive candidates per thread
+    constexpr u32 PT = lyn::CAND_MAX / WG;
+    u32 cnt = 0;
+    for (u32 e = 0; e < PT; ++e) {
+        const u32 i = tid * PT + e;
+        if (i < n && in[i] == S[i]) ++cnt;
+    }
+    const u32 incl = wave_incl_scan(cnt, OpAddU(), 0u);
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    u32 off = incl - cnt, total = 0;
+    for (u32 w = 0; w < WG / 64; ++w) {
+        if (w < (tid >> 6)) off += wsum[w];
+        total += wsum[w];
+    }
+    for (u32 e = 0; e < PT; ++e) {
+        const u32 i = tid * PT + e;
+        if (i < n && in[i] == S[i]) {
+            stack[base + off++] = S[i];
+            flag[S[i]] = 1;
+        }
+    }
+    if (tid == 0) fcount[b] = total;
+}
+
+}  // namespace
+
+// KOLM_LYN_FAST = 0 / 1 (read per call: tests and A/B runs; default on): the fast route
+bool lyn_fast_mode() {
+    if (const char* e = getenv("KOLM_LYN_FAST")) return atoi(e) != 0;
+    return true;
+}
+// the budgets: compile-time constants, lowered (LCP: also raised) by test overrides
+static u32 lyn_env(const char* name, u32 dflt, u32 lo, u32 hi) {
+    if (const char* e = getenv(name)) return (u32)std::min<u64>(hi, std::max<u64>(lo, strtoull(e, nullptr, 10)));
+    return dflt;
+}
+
 // KOLM_DUVAL_PROF=1 (debug): per-phase wall-clock of k_duval_span and k_duval_merge
 u64* dprof_buf() {
     static u64* prof = nullptr;
@@ -1068,10 +1306,11 @@ u32 duval_span_bytes(const Geom& geo) {
     (void)geo;
     return DUVAL_CH * 64;
 }
+u32 lyn_tiles_per_block(const Geom& geo) { return (geo.bs + lyn::TILE - 1) / lyn::TILE; }
 
-void launch_lyndon(const Geom& geo, const u8* text, u8* flag, u8* FEd, u32* fstart, uint4* fpre, u32* nfac,
-                   u32* stack, u32* fcount, u32* tile_tmp, hipStream_t s, KTimer* kt) {
-    if (!geo.N) return;
+bool launch_lyndon(const Geom& geo, const u8* text, u8* flag, u8* FEd, u32* fstart, uint4* fpre, u32* nfac,
+                   u32* stack, u32* fcount, u32* tile_tmp, u64* lyn_tmp, u32* lyn_route, hipStream_t s, KTimer* kt) {
+    if (!geo.N) return false;
     TileGeom tg{geo, (geo.bs + TILE - 1) / TILE};
     const u32 nt = tg.tpb * geo.nb;
     u32* A = tile_tmp;        // [nt]
@@ -1081,14 +1320,40 @@ void launch_lyndon(const Geom& geo, const u8* text, u8* flag, u8* FEd, u32* fsta
     const u32 nch = cpb * geo.nb;
     const u64 N = geo.N;
     KOLM_HIP_CHECK(hipMemsetAsync(flag, 0, geo.N, s));
+    // Fast route first: its candidate lists borrow the blocks' ranges of fstart, which the Duval
+    // kernels rewrite for the blocks they still take.
+    const bool fast = lyn_fast_mode();
+    const u32* route = nullptr;
+    if (fast) {
+        const u32 ltpb = lyn_tiles_per_block(geo), lnt = ltpb * geo.nb;
+        const u32 cap = lyn_env("KOLM_LYN_CAND_MAX", lyn::CAND_MAX, 1, lyn::CAND_MAX);
+        const u32 lcp_cap = lyn_env("KOLM_LYN_LCP_MAX", lyn::LCP_MAX, 0, lyn::LCP_LIMIT);
+        u64* tmin = lyn_tmp;        // [lnt]
+        u64* tin = lyn_tmp + lnt;   // [lnt]
+        u32* ccount = lyn_route + geo.nb;
+        {
+            KScope k(kt, KT_LYNDON, "k_lyn_min", N);  // text once
+            k_lyn_min<<<lnt, WG, 0, s>>>(geo, ltpb, text, tmin);
+        }
+        {
+            KScope k(kt, KT_LYNDON, "k_lyn_cand", (u64)lnt * 32);  // + the live tiles' text
+            k_lyn_scan<<<geo.nb, WG, 0, s>>>(tmin, tin, ltpb, lyn_route, ccount);
+            k_lyn_cand<<<lnt, WG, 0, s>>>(geo, ltpb, text, tmin, tin, cap, lyn_route, ccount, fstart);
+        }
+        {
+            KScope k(kt, KT_LYNDON, "k_lyn_resolve", (u64)geo.nb * 8);
+            k_lyn_resolve<<<geo.nb, WG, 0, s>>>(geo, text, cap, lcp_cap, lyn_route, ccount, fstart, stack, fcount, flag);
+        }
+        route = lyn_route;
+    }
     {
         KScope k(kt, KT_LYNDON, "k_duval_span", N);  // text once (+ 4 B per factor start)
-        k_duval_span<64><<<nch, 64, 0, s>>>(geo, cpb, text, fstart, fpre, nfac, dprof_buf(), DUVAL_WAVE_W, 1u);
+        k_duval_span<64><<<nch, 64, 0, s>>>(geo, cpb, text, fstart, fpre, nfac, dprof_buf(), DUVAL_WAVE_W, 1u, route);
     }
     {
         KScope k(kt, KT_LYNDON, "k_duval_merge", (u64)nch * 8);
         k_duval_merge<<<geo.nb, 64, 0, s>>>(geo, cpb, span, text, fstart, fpre, nfac, stack, fcount, flag,
-                                             dprof_buf());
+                                             dprof_buf(), route);
     }
     if (u64* prof = dprof_buf()) {
         u64 h[40];
@@ -1114,6 +1379,7 @@ void launch_lyndon(const Geom& geo, const u8* text, u8* flag, u8* FEd, u32* fsta
         KScope k(kt, KT_LYNDON, "k_fed", 2 * N);  // flag 1 + FEd 1
         k_fed<<<nt, WG, 0, s>>>(tg, flag, B, FEd);
     }
+    return fast;
 }
 
 void launch_prevc(const Geom& geo, const u8* text, const u8* flag, Factors fac, u8* prevc, hipStream_t s) {

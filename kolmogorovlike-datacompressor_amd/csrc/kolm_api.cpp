@@ -183,6 +183,11 @@ struct kolm_ctx {
     bool dedup = false;
     kolm_dedup_report drep{};
     hipEvent_t evd[2] = {};        // dedup: the event pair around its kernels
+    // Lyndon fast route (kolm_ctx_lyndon_report): the last batch's block count, whether the fast
+    // route ran and the stream it ran on; the route words stay in the "lyn_route" buffer
+    u32 lyn_nb = 0;
+    bool lyn_fast = false;
+    hipStream_t lyn_stream = nullptr;
     // pinned host staging: an upload ring (input chunks) and the result buffer of
     // kolm_compress_fixed (container bytes, valid until the next call on this context)
     static constexpr int NSTAGE = 4;
@@ -792,10 +797,13 @@ struct Pipeline {
         const u64 N = geo.N;
         const u64 ntiles = (u64)((geo.bs + TILE - 1) / TILE) * geo.nb + 16;
         const u64 nch = (geo.bs + duval_span_bytes(geo) - 1) / duval_span_bytes(geo) * (u64)geo.nb + 1;
-        launch_lyndon(geo, text, c->get<u8>("flag", N), c->get<u8>("FEd", N),
+        c->lyn_fast = launch_lyndon(geo, text, c->get<u8>("flag", N), c->get<u8>("FEd", N),
                       c->get<u32>("lyn_fstart", N), c->get<uint4>("lyn_fpre", nch * 128),
                       c->get<u32>("lyn_nfac", nch), c->get<u32>("lyn_stack", N), c->get<u32>("lyn_fcount", geo.nb + 1), c->get<u32>("lyn_t1", 2 * ntiles + 16),
-                      c->active, c->kt());
+                      c->get<u64>("lyn_tmin", 2 * (u64)lyn_tiles_per_block(geo) * geo.nb + 2),
+                      c->get<u32>("lyn_route", 2 * (u64)geo.nb + 2), c->active, c->kt());
+        c->lyn_nb = geo.nb;
+        c->lyn_stream = c->active;
     }
     Factors factors() { return Factors{c->get<u32>("lyn_stack", geo.N), c->get<u32>("lyn_fcount", geo.nb + 1)}; }
     // omega-order of all rotations of the Lyndon factors + BBWT gather -> "bbwt"
@@ -3254,6 +3262,28 @@ int kolm_ctx_dedup_report(kolm_ctx* c, kolm_dedup_report* rep) {
     std::lock_guard<std::mutex> g(c->mu);
     *rep = c->drep;
     return KOLM_OK;
+}
+
+int kolm_ctx_lyndon_report(kolm_ctx* c, uint32_t* accepted, uint32_t* fallback) {
+    if (!c) c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    if (!accepted || !fallback) return KOLM_EARG;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        *accepted = 0;
+        *fallback = c->lyn_nb;
+        if (!c->lyn_nb || !c->lyn_fast) return KOLM_OK;
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        KOLM_HIP_CHECK(hipStreamSynchronize(c->lyn_stream));
+        std::vector<u32> route(c->lyn_nb);
+        KOLM_HIP_CHECK(hipMemcpy(route.data(), c->get<u32>("lyn_route", 2 * (u64)c->lyn_nb + 2), c->lyn_nb * sizeof(u32),
+                                 hipMemcpyDeviceToHost));
+        u32 acc = 0;
+        for (u32 r : route) acc += r == 0;
+        *accepted = acc;
+        *fallback = c->lyn_nb - acc;
+        return KOLM_OK;
+    });
 }
 
 int kolm_block_fingerprints_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,

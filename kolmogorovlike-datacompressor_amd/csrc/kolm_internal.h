@@ -344,8 +344,13 @@ void launch_update_done(u32* blk_done, u32* blk_last, const u32* blk_split, u32 
 
 // ---- k_blocks.hip: per-block scans, Lyndon factors, BBWT gather ----
 u32 duval_span_bytes(const Geom& geo);  // bytes per Duval span of this batch (launch_lyndon's choice)
-void launch_lyndon(const Geom& geo, const u8* text, u8* flag, u8* FEd, u32* fstart, uint4* fpre, u32* nfac,
-                   u32* stack, u32* fcount, u32* tile_tmp, hipStream_t s, KTimer* kt = nullptr);
+u32 lyn_tiles_per_block(const Geom& geo);  // 4 KiB tiles per block of the fast route (lyndon_core.h)
+// lyn_tmp: 2 * lyn_tiles_per_block * nb words of 8 bytes; lyn_route: 2 * nb words, the first nb the
+// blocks' route words (0: resolved by the fast route, else by Duval).  Returns whether the fast
+// route ran (KOLM_LYN_FAST); if not, lyn_route is not written.
+bool launch_lyndon(const Geom& geo, const u8* text, u8* flag, u8* FEd, u32* fstart, uint4* fpre, u32* nfac,
+                   u32* stack, u32* fcount, u32* tile_tmp, u64* lyn_tmp, u32* lyn_route, hipStream_t s,
+                   KTimer* kt = nullptr);
 void launch_prevc(const Geom& geo, const u8* text, const u8* flag, Factors fac, u8* prevc, hipStream_t s);
 void launch_bbwt_gather(const Geom& geo, const u32* SA, const u8* prevc, u8* out, hipStream_t s);
 // early BBWT gather: bm[slot] bit = the slot lies in one of the *ncur_dev (<= bound) segments of cur;

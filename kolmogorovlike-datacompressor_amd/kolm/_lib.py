@@ -223,6 +223,7 @@ SIGNATURES = [
     ("kolm_ctx_set_dedup", I32, [P, I32]),
     ("kolm_set_dedup", I32, [I32]),
     ("kolm_ctx_dedup_report", I32, [P, ctypes.POINTER(DedupReport)]),
+    ("kolm_ctx_lyndon_report", I32, [P, ctypes.POINTER(U32), ctypes.POINTER(U32)]),
     ("kolm_block_fingerprints_device", I32, [P, P, P, U32, P]),
     ("kolm_find_duplicates_device", I32, [P, P, P, U32, P, ctypes.POINTER(DedupReport)]),
     ("kolm_dedup_plan", I32, [P, P, P, U32, U32, P, P, P, P, P, P, P, P, P]),
@@ -344,6 +345,17 @@ def dedup_report(ctx=None) -> dict:
     if rc:
         raise KolmError(rc, "kolm_ctx_dedup_report")
     return rep.as_dict()
+
+
+def lyndon_report(ctx=None) -> dict:
+    """Routes of the Lyndon factorisation of ctx's (None: the default context's) last batch
+    (kolm_ctx_lyndon_report): blocks resolved from prefix-minimum candidates (accepted) and blocks
+    left to the Duval kernels (fallback)."""
+    acc, fb = U32(0), U32(0)
+    rc = load().kolm_ctx_lyndon_report(ctx, ctypes.byref(acc), ctypes.byref(fb))
+    if rc:
+        raise KolmError(rc, "kolm_ctx_lyndon_report")
+    return {"accepted": int(acc.value), "fallback": int(fb.value)}
 
 
 _last_dedup: dict = {}
