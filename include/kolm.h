@@ -55,6 +55,8 @@ extern "C" {
 #define KOLM_ERANGE (-7)   /* a container field overflows (PY: struct.error) */
 #define KOLM_EVERIFY (-8)  /* verify on: an encode entry point produced a payload that does not
                               decode to its input (message names block, method, offset) */
+#define KOLM_ECHECKSUM (-9) /* decoded bytes do not match the expected CRC-32 (message: block,
+                              method, expected, got) */
 
 /* Candidate method ids (index into PY _select_encoders(), PY:2152-2165). */
 #define KOLM_M_RAW 0
@@ -496,6 +498,72 @@ int kolm_dedup_plan(const uint32_t* lens, const uint64_t* fps, const int32_t* fo
                     uint32_t fp_bits, const uint32_t* differ, uint32_t* pairs, uint32_t* rep, uint32_t* distinct,
                     kolm_range_seg* compact, const uint64_t* distinct_off, uint64_t* payload_off,
                     kolm_range_seg* expand, uint32_t* counts);
+
+/* ---- checksums: block and stream CRC-32 of resident bytes (crc_core.h, k_crc.hip) --- */
+/* The container carries no checksum and does not grow one.  These calls compute the standard
+ * CRC-32 (zlib / gzip / PNG: zlib.crc32) of every block on the device while the bytes are
+ * resident there (k_crc32: one streaming read, one word per block comes back; the length term and
+ * every combine are host arithmetic).  The words can be persisted (kolm.checksums: a sidecar
+ * file) and reproduced with standard tools. */
+#define KOLM_CR_NONE 0      /* kolm_check_report.first_bad_reason */
+#define KOLM_CR_MISMATCH 1  /* the block decodes to bytes with another CRC-32 */
+#define KOLM_CR_REJECTED 2  /* the decoder rejected the payload */
+typedef struct kolm_check_report {
+    uint32_t blocks;              /* blocks checked */
+    uint32_t bad_blocks;          /* of which: mismatching or rejected (0 without an expectation) */
+    uint32_t first_bad_block;     /* the lowest-numbered bad block, its method id, the expected and */
+    uint32_t first_bad_method;    /* the computed CRC-32 and the reason */
+    uint32_t first_bad_expected;
+    uint32_t first_bad_got;
+    uint32_t first_bad_reason;    /* KOLM_CR_* */
+    uint32_t stream_crc;          /* CRC-32 of the decoded stream: the blocks' words combined */
+    uint64_t bytes;               /* decoded bytes checked */
+    double ms_decode;             /* device time of the decode kernels (HIP events) */
+    double ms_crc;                /* device time of k_crc32 */
+} kolm_check_report;
+/* CRC-32 of the blocks of d_data (device; block i = [h_bounds[i], h_bounds[i+1]), h_bounds[0] = 0,
+ * non-decreasing: empty blocks are allowed and give 0, nblocks + 1 host entries, total < 2^31;
+ * any alignment): h_crc[i].  *ms (optional): device time of k_crc32. */
+int kolm_crc32_blocks_device(kolm_ctx* ctx, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                             uint32_t* h_crc, double* ms);
+/* CRC-32 of A || B from crc_a = CRC-32(A), crc_b = CRC-32(B) and len_b = |B| (host only, usable
+ * without a GPU; zlib's crc32_combine). */
+uint32_t kolm_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* Checksums while encoding (default off, or KOLM_CHECKSUMS=1 at context creation): when enabled,
+ * kolm_encode_blocks, kolm_encode_blocks_device, kolm_encode_blocks_device_var and every device
+ * batch of kolm_compress_fixed run k_crc32 once over the batch's resident input, on the index
+ * stream behind the event the sort stream (the critical path) starts from, so the pass runs beside
+ * that chain; the words come back behind the batch's own final synchronisation.
+ * Block numbers are container numbers, with dedup on too; independent of verify.  The contexts of
+ * kolm_encode_blocks_multi ignore the switch.  Disabled: no extra launch, allocation or
+ * synchronisation.  The container's bytes do not depend on the switch. */
+int kolm_ctx_set_checksums(kolm_ctx* ctx, int enable);
+int kolm_set_checksums(int enable);  /* default context */
+/* The CRC-32 words of the last encode call of ctx (NULL: the default context), in container block
+ * order, summed over its device batches: *nblocks (optional) their count (0 when the call ran with
+ * checksums disabled), crc[0, cap) (optional; KOLM_ECAP when cap < the count). */
+int kolm_ctx_checksums(kolm_ctx* ctx, uint32_t* crc, uint32_t cap, uint32_t* nblocks);
+/* kolm_decode_blocks, and the CRC-32 of every decoded block taken on the device while the output
+ * is resident: got[i] (optional).  With expect (optional, nblocks words) a block whose word
+ * differs makes the call return KOLM_ECHECKSUM (kolm_last_error names the lowest-numbered such
+ * block, its method, the expected and the computed word); out is still filled. */
+int kolm_decode_blocks_crc(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
+                           const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap,
+                           const uint32_t* expect, uint32_t* got);
+/* A whole container against its blocks' CRC-32 words without the original data (host buffers,
+ * default context): the TOC by kolm_toc_read (KOLM_EFORMAT as there), the payloads go up, the
+ * blocks are decoded in the groups of kolm_verify_blocks_device ($KOLM_VERIFY_BYTES) and k_crc32
+ * runs over each group's scratch; only the words come down: got[0, cap) (optional; KOLM_ECAP
+ * when cap < the block count), *rep the summary.  expect (nblocks words) == NULL only computes:
+ * the manifest of an existing container.  KOLM_OK whenever the check ran. */
+int kolm_check_container(const uint8_t* container, uint64_t cn, const uint32_t* expect, uint32_t* got, uint32_t cap,
+                         kolm_check_report* rep);
+/* The expected CRC-32 of every block of the reader's container (nblocks = its block count; crc ==
+ * NULL clears).  Once set, every group decode of kolm_reader_read / kolm_reader_read_device takes
+ * the CRC-32 of the group's decoded blocks in the scratch and compares the words on the host
+ * before anything is gathered (one more round trip per group): a mismatch makes the call return
+ * KOLM_ECHECKSUM, and nothing is written to the output. */
+int kolm_reader_set_checksums(kolm_reader* r, const uint32_t* crc, uint32_t nblocks);
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (kolm_comm.cpp) ------------- */
 /* The only data exchange of the multi-GPU path: blocks are independent (PY:2350-2369), so

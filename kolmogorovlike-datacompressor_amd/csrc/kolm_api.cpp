@@ -28,6 +28,7 @@
 #include "kolm_internal.h"
 #include "verify_core.h"
 #include "dedup_core.h"
+#include "crc_core.h"
 
 using namespace kolm;
 
@@ -183,6 +184,31 @@ struct kolm_ctx {
     bool dedup = false;
     kolm_dedup_report drep{};
     hipEvent_t evd[2] = {};        // dedup: the event pair around its kernels
+    // checksums (kolm_ctx_set_checksums; KOLM_CHECKSUMS=1): every encode batch takes the CRC-32 of
+    // its blocks on the resident text (crc_enqueue / crc_collect below); ccrc accumulates over the
+    // batches of one call.  The rest is the state of one CRC pass, used by every caller of the
+    // pair under the context lock: the table words on the device (an allocation of its own, made
+    // at the first pass: the per-batch clean-up of the named buffers never touches it), the host
+    // arrays the pass's uploads read (alive until the pass is collected), the pinned landing
+    // buffer of the raw words and the events around the kernel and behind the read-back
+    bool checksums = false;
+    std::vector<u32> ccrc;
+    struct CrcPass {
+        u32* d_tab = nullptr;
+        u32* h_raw = nullptr;
+        size_t h_cap = 0;
+        std::vector<u32> hb, scan;  // block bounds (nb + 1) and the scan of the run counts
+        u32 nb = 0;
+        // what crc_prepare leaves for crc_launch: the text, its geometry and the raw words' buffer
+        const u8* text = nullptr;
+        u64 N = 0;
+        u32 bs = 0;
+        bool var = false;
+        u32* draw = nullptr;
+        bool armed = false;     // prepared, not launched yet
+        bool launched = false;
+        hipEvent_t ev[3] = {};  // kernel start, kernel end, words on the host
+    } crc;
     // Lyndon fast route (kolm_ctx_lyndon_report): the last batch's block count, whether the fast
     // route ran and the stream it ran on; the route words stay in the "lyn_route" buffer
     u32 lyn_nb = 0;
@@ -1027,6 +1053,10 @@ void verify_message(const kolm_verify_report& r);  // kolm_last_error text of a 
 int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
                  const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
                  kolm_stats* stats);
+void crc_launch(kolm_ctx* c, hipStream_t s);  // checksums: the prepared CRC pass, if one is armed (below)
+int decode_blocks_host(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
+                       const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap, bool with_crc,
+                       const uint32_t* expect, uint32_t* got);  // kolm_decode_blocks[_crc] (with the verify step below)
 
 // the checks of a batch that depend on the candidate mask (N bytes, longest block bs)
 int check_mask(u32 mask, u64 N, u32 bs) {
@@ -1089,6 +1119,9 @@ int encode_each(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bound
     u64* d_bits = c->get<u64>("bits", (u64)nb * 8);
     KOLM_HIP_CHECK(hipMemsetAsync(d_bits, 0, sizeof(u64) * 8 * nb, ms));
     KOLM_HIP_CHECK(hipEventRecord(ev[0], ms));
+    // checksums on: the armed CRC pass goes behind ev[0] on the index stream, so the sort stream
+    // (which waits for ev[0] alone) starts without it and the pass runs beside its chain
+    crc_launch(c, ms);
     // Re-Pair (candidate 9): persistent workgroups (one per block) on their own stream,
     // launched first so they take their CUs while the sort / LZ77 chains queue beside them
     const bool want_rp = (mask >> KOLM_M_REPAIR) & 1u;
@@ -1478,6 +1511,7 @@ int ctx_create(int device, kolm_ctx** out) {
         c->serial = getenv("KOLM_SERIAL") && atoi(getenv("KOLM_SERIAL")) != 0;
         c->verify = getenv("KOLM_VERIFY") && atoi(getenv("KOLM_VERIFY")) != 0;
         c->dedup = getenv("KOLM_DEDUP") && atoi(getenv("KOLM_DEDUP")) != 0;
+        c->checksums = getenv("KOLM_CHECKSUMS") && atoi(getenv("KOLM_CHECKSUMS")) != 0;
         for (auto& e : c->evj) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evr) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evg) KOLM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1501,6 +1535,7 @@ kolm_ctx* need_default() {
 // start of an encode call (context lock held): the verify report covers this call's batches
 void verify_begin(kolm_ctx* c, u32 first_block = 0) {
     c->drep = kolm_dedup_report{};  // the dedup report covers this call's batches too (zero when off)
+    c->ccrc.clear();                // and the checksums (none when off)
     if (!c->verify) return;
     c->vrep = kolm_verify_report{};
     c->vshard = first_block;
@@ -1618,6 +1653,10 @@ int kolm_ctx_destroy(kolm_ctx* c) {
         for (auto& e : c->evd)
             if (e) KOLM_HIP_CHECK(hipEventDestroy(e));
         for (auto& e : c->evpool) KOLM_HIP_CHECK(hipEventDestroy(e));
+        for (auto& e : c->crc.ev)
+            if (e) KOLM_HIP_CHECK(hipEventDestroy(e));
+        if (c->crc.d_tab) KOLM_HIP_CHECK(hipFree(c->crc.d_tab));
+        if (c->crc.h_raw) KOLM_HIP_CHECK(hipHostFree(c->crc.h_raw));
         KOLM_HIP_CHECK(hipHostFree(c->h_cnt));
         if (c->h_rt) KOLM_HIP_CHECK(hipHostFree(c->h_rt));
         if (c->h_tail) KOLM_HIP_CHECK(hipHostFree(c->h_tail));
@@ -2151,6 +2190,7 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
             P.off.assign(nbr + 1, 0);
             c->verify = verify;
             c->dedup = dedup;
+            c->checksums = false;  // the multi-device contexts ignore the switch (kolm.h)
             verify_begin(c, b0[r]);
             int rc = encode_batch(c, d, n, block_size, nullptr, 0, cand_mask & KOLM_FULL_MASK,
                                   force_method ? force_method + b0[r] : nullptr, arena, dcap,
@@ -2699,25 +2739,7 @@ static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off
 
 int kolm_decode_blocks(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
                        const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap) {
-    kolm_ctx* c = need_default();
-    if (!c) return KOLM_ENOINIT;
-    if (nblocks && (!payloads || !payload_off || !methods || !orig_lens || !out)) return KOLM_EARG;
-    u64 total = 0;
-    if (int rc = check_decode(payload_off, methods, orig_lens, nblocks, out_cap, total)) return rc;
-    if (nblocks == 0) return KOLM_OK;
-    return guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        const u32 nb = nblocks;
-        const u64 ptotal = payload_off[nb] - payload_off[0];
-        u8* dpay = c->get<u8>("dec_pay", ptotal + 64);
-        u8* dout = c->get<u8>("dec_out", total + 64);
-        if (ptotal)
-            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, payloads + payload_off[0], ptotal, hipMemcpyHostToDevice, c->stream));
-        if (int rc = decode_batch(c, dpay, payload_off, methods, orig_lens, nb, total, dout, nullptr)) return rc;
-        KOLM_HIP_CHECK(hipMemcpy(out, dout, total, hipMemcpyDeviceToHost));
-        return KOLM_OK;
-    });
+    return decode_blocks_host(payloads, payload_off, methods, orig_lens, nblocks, out, out_cap, false, nullptr, nullptr);
 }
 
 int kolm_decode_blocks_device(kolm_ctx* c, const void* d_payloads, const uint64_t* payload_off,
@@ -2748,6 +2770,144 @@ u64 verify_group_limit() {
     return std::min<u64>(lim, (1ull << 31) - 1);
 }
 
+// The group that begins at block g0: the blocks [g0, g1) whose decoded bytes (tot) stay under lim;
+// a single block always forms one.  Returns g1.
+u32 verify_group(const u64* bounds, u32 nb, u32 g0, u64 lim, u64& tot) {
+    u32 g1 = g0 + 1;
+    tot = bounds[g1] - bounds[g0];
+    while (g1 < nb && tot + (bounds[g1 + 1] - bounds[g1]) <= lim) {
+        tot += bounds[g1 + 1] - bounds[g1];
+        ++g1;
+    }
+    return g1;
+}
+
+// ---- checksums: block CRC-32 of resident bytes (crc_core.h, k_crc.hip) ----
+const u32* crc_host_tables() {
+    static const std::vector<u32> t = [] {
+        std::vector<u32> v(crc::TABLE_WORDS);
+        crc::gen_tables(v.data());
+        return v;
+    }();
+    return t.data();
+}
+
+// One CRC pass over the nb blocks of d_text: fixed blocks of bs bytes over [0, N) (hb == null) or
+// the blocks [hb[i], hb[i + 1]) (hb[0] = 0, non-decreasing, hb[nb] = N < 2^31).  crc_prepare makes
+// every allocation and host array; crc_launch puts the stream work on s: the raw words are zeroed,
+// computed and copied to pinned host memory behind each other, no host wait; crc_collect finishes
+// them.  crc_enqueue = prepare + launch.  One pass at a time per context (its lock is held).
+void crc_prepare(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* hb, u32 nb) {
+    kolm_ctx::CrcPass& p = c->crc;
+    if (!p.d_tab) {
+        KOLM_HIP_CHECK(hipMalloc((void**)&p.d_tab, sizeof(u32) * crc::TABLE_WORDS));
+        KOLM_HIP_CHECK(hipMemcpy(p.d_tab, crc_host_tables(), sizeof(u32) * crc::TABLE_WORDS, hipMemcpyHostToDevice));
+    }
+    for (auto& e : p.ev)
+        if (!e) KOLM_HIP_CHECK(hipEventCreate(&e));
+    if (p.h_cap < nb) {
+        if (p.h_raw) KOLM_HIP_CHECK(hipHostFree(p.h_raw));
+        p.h_raw = nullptr;
+        p.h_cap = 0;
+        const size_t cap = std::max<size_t>((size_t)nb + (nb >> 2), 1024);
+        KOLM_HIP_CHECK(hipHostMalloc((void**)&p.h_raw, cap * sizeof(u32), hipHostMallocDefault));
+        p.h_cap = cap;
+    }
+    p.nb = nb;
+    p.launched = false;
+    p.armed = false;
+    p.hb.assign((size_t)nb + 1, 0);
+    for (u32 b = 0; b <= nb; ++b) p.hb[b] = hb ? hb[b] : (u32)std::min<u64>(N, (u64)b * bs);
+    if (nb == 0 || N == 0) return;  // empty blocks alone: raw = 0
+    p.text = d_text, p.N = N, p.bs = bs, p.var = hb != nullptr;
+    p.draw = c->get<u32>("crc_raw", nb);
+    if (hb) {  // variable geometry: the blocks' run counts differ
+        p.scan.assign((size_t)nb + 1, 0);
+        for (u32 b = 0; b < nb; ++b) p.scan[b + 1] = p.scan[b] + (u32)ddp::runs(p.hb[b + 1] - p.hb[b]);  // < 2^16 + nb
+        c->get<u32>("crc_vb", (size_t)nb + 1);
+        c->get<u32>("crc_scan", (size_t)nb + 1);
+    }
+    p.armed = true;
+}
+
+// The prepared pass's stream work on s, if one is armed: launches and asynchronous copies only, no
+// allocation and no host wait (encode_each calls it between its own launches).
+void crc_launch(kolm_ctx* c, hipStream_t s) {
+    kolm_ctx::CrcPass& p = c->crc;
+    if (!p.armed) return;
+    p.armed = false;
+    const u32 nb = p.nb;
+    KOLM_HIP_CHECK(hipMemsetAsync(p.draw, 0, sizeof(u32) * nb, s));
+    Geom geo;
+    const u32* dscan = nullptr;
+    u64 nruns = 0;
+    if (p.var) {  // base / end need the bounds alone
+        geo = Geom{};
+        geo.N = p.N, geo.nb = nb;
+        geo.bs = 1;
+        for (u32 b = 0; b < nb; ++b) geo.bs = std::max(geo.bs, p.hb[b + 1] - p.hb[b]);
+        u32* dvb = c->get<u32>("crc_vb", (size_t)nb + 1);
+        u32* d = c->get<u32>("crc_scan", (size_t)nb + 1);
+        KOLM_HIP_CHECK(hipMemcpyAsync(dvb, p.hb.data(), sizeof(u32) * ((size_t)nb + 1), hipMemcpyHostToDevice, s));
+        KOLM_HIP_CHECK(hipMemcpyAsync(d, p.scan.data(), sizeof(u32) * ((size_t)nb + 1), hipMemcpyHostToDevice, s));
+        geo.vb = dvb, geo.hvb = p.hb.data();
+        dscan = d;
+        nruns = p.scan[nb];
+    } else {
+        geom_init(geo, p.N, p.bs);
+        nruns = (u64)nb * ddp::runs(p.bs);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(p.ev[0], s));
+    launch_crc32(p.text, geo, dscan, nruns, p.d_tab, p.draw, s);
+    KOLM_HIP_CHECK(hipEventRecord(p.ev[1], s));
+    KOLM_HIP_CHECK(hipMemcpyAsync(p.h_raw, p.draw, sizeof(u32) * nb, hipMemcpyDeviceToHost, s));
+    KOLM_HIP_CHECK(hipEventRecord(p.ev[2], s));
+    p.launched = true;
+}
+
+void crc_enqueue(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* hb, u32 nb, hipStream_t s) {
+    crc_prepare(c, d_text, N, bs, hb, nb);
+    crc_launch(c, s);
+}
+
+// The CRC-32 words of the pass enqueued last: out[0, nb).  Waits for the read-back's event (passed
+// already when the caller has synchronised the stream).  Returns the kernel's device time and,
+// with timing on, adds the launch to the per-kernel table.
+double crc_collect(kolm_ctx* c, u32* out) {
+    kolm_ctx::CrcPass& p = c->crc;
+    double ms = 0.0;
+    if (p.launched) {
+        KOLM_HIP_CHECK(hipEventSynchronize(p.ev[2]));
+        ms = ev_ms(p.ev[0], p.ev[1]);
+        if (c->timing) {
+            kolm_ctx::Acc& a = c->kacc["k_crc32"];
+            a.fam = KOLM_KT_EMIT;
+            a.strm = 0;
+            a.ms += ms;
+            a.launches += 1;
+            a.bytes += p.hb[p.nb];
+        }
+    }
+    for (u32 b = 0; b < p.nb; ++b) out[b] = crc::finish(p.launched ? p.h_raw[b] : 0u, p.hb[b + 1] - p.hb[b]);
+    p.launched = false;
+    return ms;
+}
+
+// The pass over the blocks of lengths lens[0, n) that lie back to back at d (a decode scratch):
+// out[0, n).  Returns the kernel's device time.
+double crc_blocks_at(kolm_ctx* c, const u8* d, const u32* lens, u32 n, u32* out) {
+    std::vector<u32> hb((size_t)n + 1, 0);
+    for (u32 i = 0; i < n; ++i) hb[i + 1] = hb[i] + lens[i];
+    crc_enqueue(c, d, hb[n], 0, hb.data(), n, c->stream);
+    return crc_collect(c, out);
+}
+
+void checksum_message(u32 block, u32 method, u32 expected, u32 got) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "checksum: block %u (method %u): expected CRC-32 %08x, got %08x", block, method, expected, got);
+    set_err(msg);
+}
+
 // Blocks [0, nb) of d_data (block i = [bounds[i], bounds[i + 1])) against their payloads at
 // d_pay + (poff[i] - poff[0]); both device-resident and complete as far as c->stream sees.
 // Groups of blocks whose decoded bytes stay under the limit (a single block always forms
@@ -2775,12 +2935,8 @@ int verify_run(kolm_ctx* c, const u8* d_data, const u64* bounds, u32 nb, const u
     const size_t p0 = c->pend.size();
     std::vector<u32> lens, st, fb;
     for (u32 g0 = 0; g0 < nb;) {
-        u32 g1 = g0 + 1;
-        u64 tot = bounds[g1] - bounds[g0];
-        while (g1 < nb && tot + (bounds[g1 + 1] - bounds[g1]) <= lim) {
-            tot += bounds[g1 + 1] - bounds[g1];
-            ++g1;
-        }
+        u64 tot = 0;
+        const u32 g1 = verify_group(bounds, nb, g0, lim, tot);
         const u32 n = g1 - g0;
         lens.resize(n);
         for (u32 i = 0; i < n; ++i) lens[i] = (u32)(bounds[g0 + i + 1] - bounds[g0 + i]);
@@ -2858,6 +3014,98 @@ int verify_encoded(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bo
     if (c->vrep.bad_blocks == bad0) return KOLM_OK;
     verify_message(c->vrep);
     return KOLM_EVERIFY;
+}
+
+// kolm_decode_blocks and kolm_decode_blocks_crc: host payloads up, one decode batch, the output
+// down.  with_crc: k_crc32 over the output while it is resident, got / expect as kolm.h says.
+int decode_blocks_host(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
+                       const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap, bool with_crc,
+                       const uint32_t* expect, uint32_t* got) {
+    kolm_ctx* c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    if (nblocks && (!payloads || !payload_off || !methods || !orig_lens || !out)) return KOLM_EARG;
+    u64 total = 0;
+    if (int rc = check_decode(payload_off, methods, orig_lens, nblocks, out_cap, total)) return rc;
+    if (nblocks == 0) return KOLM_OK;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        const u32 nb = nblocks;
+        const u64 ptotal = payload_off[nb] - payload_off[0];
+        u8* dpay = c->get<u8>("dec_pay", ptotal + 64);
+        u8* dout = c->get<u8>("dec_out", total + 64);
+        if (ptotal)
+            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, payloads + payload_off[0], ptotal, hipMemcpyHostToDevice, c->stream));
+        if (int rc = decode_batch(c, dpay, payload_off, methods, orig_lens, nb, total, dout, nullptr)) return rc;
+        std::vector<u32> words;
+        if (with_crc) {
+            words.resize(nb);
+            crc_blocks_at(c, dout, orig_lens, nb, words.data());
+        }
+        KOLM_HIP_CHECK(hipMemcpy(out, dout, total, hipMemcpyDeviceToHost));
+        if (with_crc && got) std::copy(words.begin(), words.end(), got);
+        if (with_crc && expect)
+            for (u32 i = 0; i < nb; ++i)
+                if (words[i] != expect[i]) {
+                    checksum_message(i, methods[i], expect[i], words[i]);
+                    return KOLM_ECHECKSUM;
+                }
+        return KOLM_OK;
+    });
+}
+
+// The nb blocks of lengths lens whose payloads are resident at d_pay + (poff[i] - poff[0]): decoded
+// in verify_run's groups into scratch, k_crc32 over each group's scratch, only the words come
+// back: got (optional).  expect (optional): the words to compare with.  Context lock held.
+int check_run(kolm_ctx* c, const u32* lens, u32 nb, const u8* d_pay, const u64* poff, const u32* methods,
+              const u32* expect, u32* got, kolm_check_report& rep) {
+    std::vector<u64> bounds((size_t)nb + 1, 0);
+    for (u32 i = 0; i < nb; ++i) {  // the method ids before the first launch, by container block number
+        if (methods[i] >= 32 || !((KOLM_DECODE_MASK >> methods[i]) & 1u)) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "block %u: method %u is not decoded on the device", i, methods[i]);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        bounds[i + 1] = bounds[i] + lens[i];  // offsets and sizes: check_decode, per group, before its launch
+    }
+    const u64 lim = verify_group_limit();
+    c->active = c->stream;
+    std::vector<u32> st, words;
+    u32 stream_crc = 0;
+    for (u32 g0 = 0; g0 < nb;) {
+        u64 tot = 0, total = 0;
+        const u32 g1 = verify_group(bounds.data(), nb, g0, lim, tot);
+        const u32 n = g1 - g0;
+        if (int rc = check_decode(poff + g0, methods + g0, lens + g0, n, tot, total)) return rc;
+        u8* dec = c->get<u8>("chk_dec", tot + 64 + ddp::WORD);
+        double ms = 0.0;
+        if (int rc = decode_batch(c, d_pay + (poff[g0] - poff[0]), poff + g0, methods + g0, lens + g0, n, tot, dec, &ms, &st))
+            return rc;
+        words.resize(n);
+        rep.ms_crc += crc_blocks_at(c, dec, lens + g0, n, words.data());
+        rep.ms_decode += ms;
+        for (u32 i = 0; i < n; ++i) {
+            const u32 b = g0 + i;
+            if (got) got[b] = words[i];
+            stream_crc = crc::combine(stream_crc, words[i], lens[b]);
+            const bool bad = st[i] || (expect && expect[b] != words[i]);
+            if (!bad) continue;
+            if (rep.bad_blocks++ == 0) {
+                rep.first_bad_block = b;
+                rep.first_bad_method = methods[b];
+                rep.first_bad_expected = expect ? expect[b] : 0u;
+                rep.first_bad_got = words[i];
+                rep.first_bad_reason = st[i] ? KOLM_CR_REJECTED : KOLM_CR_MISMATCH;
+            }
+        }
+        rep.blocks += n;
+        rep.bytes += tot;
+        g0 = g1;
+    }
+    rep.stream_crc = stream_crc;
+    if (c->timing) c->timing_collect_tail(0, nullptr);
+    return KOLM_OK;
 }
 
 }  // namespace
@@ -2971,6 +3219,8 @@ struct kolm_reader {
     // k_range_gather (payload compaction): hipMalloc aligns it to 256 bytes and it is padded by
     // 64 + 16 bytes, the decoders' read-ahead plus the gather's last aligned word.
     u8* dpay = nullptr;
+    // the blocks' expected CRC-32 (kolm_reader_set_checksums): nb words, or empty = reads are not checked
+    std::vector<u32> crcs;
 };
 
 namespace {
@@ -3101,7 +3351,47 @@ void dedup_find(kolm_ctx* c, const u8* d_text, const Geom& geo, const std::vecto
     rep.bytes += geo.N;
 }
 
+int encode_dedup(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
+                 const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
+                 kolm_stats* stats);
+
+// The outer wrapper.  Checksums off: encode_dedup, the path as it was.  On: one k_crc32 pass over
+// the ORIGINAL text (block numbers are container numbers with dedup on too).  It is prepared here
+// (allocations, host arrays) and launched by encode_each on the index stream right behind ev[0]:
+// the stream every caller has ordered behind the text's upload (kolm_compress_fixed: the wait on
+// the upload event; the other entry points: stream order).  The sort stream, the critical path,
+// waits for ev[0] alone, so the pass runs beside its chain, in front of the index stream's size
+// counters and LZ77 parse.  Nothing waits for it: the words are collected after the batch has
+// returned synchronised, and appended to c->ccrc.
 int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
+                 const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
+                 kolm_stats* stats) {
+    if (!c->checksums)
+        return encode_dedup(c, d_text, N, bs, h_bounds, nbv, mask, h_force, d_arena, arena_cap, h_sizes, h_method, h_off,
+                            stats);
+    // the geometry checks of encode_each before the first launch
+    if (h_bounds) {
+        if (int e = check_bounds(h_bounds, nbv)) return e;
+    } else if (int e = check_geom(N, bs)) {
+        return e;
+    }
+    const u64 n = h_bounds ? h_bounds[nbv] : N;
+    const u32 nb = h_bounds ? nbv : (u32)((N + bs - 1) / bs);
+    crc_prepare(c, d_text, n, bs, h_bounds, nb);
+    struct Disarm {  // an error return or a throw before the batch's first launch: nothing was enqueued
+        kolm_ctx* c;
+        ~Disarm() { c->crc.armed = false; }
+    } disarm{c};
+    const int rc = encode_dedup(c, d_text, N, bs, h_bounds, nbv, mask, h_force, d_arena, arena_cap, h_sizes, h_method,
+                                h_off, stats);
+    const size_t at = c->ccrc.size();
+    c->ccrc.resize(at + nb);
+    crc_collect(c, c->ccrc.data() + at);
+    if (rc && rc != KOLM_EVERIFY) c->ccrc.resize(at);  // the batch was not encoded
+    return rc;
+}
+
+int encode_dedup(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
                  const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
                  kolm_stats* stats) {
     if (!c->dedup)
@@ -3380,8 +3670,12 @@ int reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint
         c->timing_reset();
         hipStream_t s = c->stream;
         c->active = s;
-        u8* dout = d_out ? static_cast<u8*>(d_out) : c->get<u8>("rd_out", want + 64);
-        std::vector<u32> gm, gl, status, scan;
+        // Checked reads write nothing to the caller's buffer on a mismatch: with several groups the
+        // ranges are packed in the context's own buffer and copied once every group has passed.
+        const bool checked = !r->crcs.empty();
+        const bool staged = checked && d_out && p.group_first.size() > 2;
+        u8* dout = d_out && !staged ? static_cast<u8*>(d_out) : c->get<u8>("rd_out", want + 64);
+        std::vector<u32> gm, gl, status, scan, words;
         std::vector<u64> gp;
         std::vector<rng::Seg> runs;
         for (u32 g = 0; g + 1 < p.group_first.size(); ++g) {
@@ -3424,6 +3718,17 @@ int reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint
                     set_err(msg);
                     return KOLM_EARG;
                 }
+            if (checked) {  // the group's blocks lie back to back in the scratch: one pass, one round trip
+                words.resize(n);
+                crc_blocks_at(c, dec, gl.data(), n, words.data());
+                for (u32 i = 0; i < n; ++i) {
+                    const u32 b = p.sel[i0 + i];
+                    if (words[i] != r->crcs[b]) {
+                        checksum_message(b, gm[i], r->crcs[b], words[i]);
+                        return KOLM_ECHECKSUM;
+                    }
+                }
+            }
             const u32 s0 = p.group_seg[g], s1 = p.group_seg[g + 1];
             if (s1 > s0) {
                 gather_segments(c, "rd_g", dec, dout, p.segs.data() + s0, s1 - s0, scan, c->ev[2], c->ev[3]);
@@ -3432,6 +3737,10 @@ int reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint
             }
         }
         if (c->timing) c->timing_collect_tail(0, nullptr);
+        if (staged && want) {  // on the context's stream and waited for: a device-to-device hipMemcpy does not wait
+            KOLM_HIP_CHECK(hipMemcpyAsync(d_out, dout, want, hipMemcpyDeviceToDevice, s));
+            c->sync();
+        }
         if (!d_out && want) KOLM_HIP_CHECK(hipMemcpy(out, dout, want, hipMemcpyDeviceToHost));
         return KOLM_OK;
     });
@@ -3528,6 +3837,128 @@ int kolm_reader_read_device(kolm_reader* r, const uint64_t* offs, const uint64_t
         if (want) return KOLM_EARG;
     }
     return reader_read(r, offs, lens, nranges, nullptr, d_out, out_cap, stats);
+}
+
+// ---- checksums (crc_core.h, k_crc.hip; the helpers stand with the verify step above) ----
+uint32_t kolm_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc::combine(crc_a, crc_b, len_b); }
+
+int kolm_crc32_blocks_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks, uint32_t* h_crc,
+                             double* ms) {
+    if (!c) return KOLM_EARG;
+    if (ms) *ms = 0.0;
+    if (nblocks == 0) return KOLM_OK;
+    if (!h_bounds || !h_crc) return KOLM_EARG;
+    if (h_bounds[0] != 0) {
+        set_err("block bounds must start at 0");
+        return KOLM_EARG;
+    }
+    std::vector<u32> hb((size_t)nblocks + 1, 0);
+    for (u32 b = 0; b < nblocks; ++b) {
+        if (h_bounds[b + 1] < h_bounds[b] || h_bounds[b + 1] >= (1ull << 31)) {
+            set_err("blocks must be contiguous, the batch smaller than 2^31 bytes");
+            return KOLM_EARG;
+        }
+        hb[b + 1] = (u32)h_bounds[b + 1];
+    }
+    if (hb[nblocks] && !d_data) return KOLM_EARG;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        crc_enqueue(c, static_cast<const u8*>(d_data), hb[nblocks], 0, hb.data(), nblocks, c->stream);
+        const double t = crc_collect(c, h_crc);
+        if (ms) *ms = t;
+        return KOLM_OK;
+    });
+}
+
+int kolm_ctx_set_checksums(kolm_ctx* c, int enable) {
+    if (!c) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->checksums = enable != 0;
+    return KOLM_OK;
+}
+
+int kolm_set_checksums(int enable) {
+    kolm_ctx* c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    return kolm_ctx_set_checksums(c, enable);
+}
+
+int kolm_ctx_checksums(kolm_ctx* c, uint32_t* crc_out, uint32_t cap, uint32_t* nblocks) {
+    if (!c) c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (nblocks) *nblocks = (u32)c->ccrc.size();
+    if (crc_out) {
+        if (cap < c->ccrc.size()) {
+            set_err("kolm_ctx_checksums: capacity too small");
+            return KOLM_ECAP;
+        }
+        std::copy(c->ccrc.begin(), c->ccrc.end(), crc_out);
+    }
+    return KOLM_OK;
+}
+
+int kolm_decode_blocks_crc(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
+                           const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap,
+                           const uint32_t* expect, uint32_t* got) {
+    return decode_blocks_host(payloads, payload_off, methods, orig_lens, nblocks, out, out_cap, true, expect, got);
+}
+
+int kolm_check_container(const uint8_t* container, uint64_t cn, const uint32_t* expect, uint32_t* got, uint32_t cap,
+                         kolm_check_report* rep) {
+    kolm_ctx* c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    if (!container && cn) return KOLM_EARG;
+    kolm_check_report r{};
+    if (rep) *rep = r;
+    u32 fields[4] = {};
+    u64 start = 0;
+    std::vector<u32> methods(65536), lens(65536);
+    std::vector<u64> poff(65537);
+    if (int rc = kolm_toc_read(container, cn, fields, &start, methods.data(), lens.data(), poff.data(), 65536)) return rc;
+    const u32 nb = fields[3];
+    if (got && cap < nb) {
+        set_err("got capacity too small");
+        return KOLM_ECAP;
+    }
+    u64 sum = 0;
+    for (u32 i = 0; i < nb; ++i) sum += lens[i];
+    if (sum != fields[2]) {  // as kolm_reader_open: the TOC's lengths do not add up to total_len
+        char msg[96];
+        snprintf(msg, sizeof msg, "Length mismatch: got %llu, expect %llu", (unsigned long long)sum,
+                 (unsigned long long)fields[2]);
+        set_err(msg);
+        return KOLM_EFORMAT;
+    }
+    if (nb == 0) return KOLM_OK;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        const u64 ptotal = poff[nb] - poff[0];
+        u8* dpay = c->get<u8>("vfy_pay", ptotal + 64);
+        if (ptotal)
+            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, container + start + poff[0], ptotal, hipMemcpyHostToDevice, c->stream));
+        return check_run(c, lens.data(), nb, dpay, poff.data(), methods.data(), expect, got, r);
+    });
+    if (rep) *rep = r;
+    return rc;
+}
+
+int kolm_reader_set_checksums(kolm_reader* r, const uint32_t* crc_in, uint32_t nblocks) {
+    if (!r || !r->c) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(r->c->mu);
+    if (!crc_in) {
+        r->crcs.clear();
+        return KOLM_OK;
+    }
+    if (nblocks != r->nb) {
+        set_err("kolm_reader_set_checksums: the block count differs from the container's");
+        return KOLM_EARG;
+    }
+    r->crcs.assign(crc_in, crc_in + nblocks);
+    return KOLM_OK;
 }
 
 int kolm_bbwt_forward(const uint8_t* in, size_t n, uint8_t* out) {

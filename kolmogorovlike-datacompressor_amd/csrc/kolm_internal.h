@@ -674,6 +674,13 @@ u32 dedup_map(u32 nb, const std::vector<u32>& pairs, const u32* differ, std::vec
 void dedup_compact(const u32* lens, u32 nb, const std::vector<u32>& distinct, std::vector<rng::Seg>& segs);
 void dedup_expand(const std::vector<u32>& rep, const std::vector<u32>& distinct, const u64* dist_off, u64* payload_off,
                   std::vector<rng::Seg>& segs);
+
+// ---- k_crc.hip: block CRC-32 (crc_core.h) ----
+// raw [nb] (zeroed by the caller on s) receives every block's raw CRC word (crc::finish on the host
+// turns it into the CRC-32).  scan / nruns as launch_block_fp; tab: the crc::TABLE_WORDS table
+// words (crc::gen_tables) on the device, 16-byte aligned.  geo is addressed through base / end
+// only.  Reads [text, text + geo.N) and nothing else.
+void launch_crc32(const u8* text, const Geom& geo, const u32* scan, u64 nruns, const u32* tab, u32* raw, hipStream_t s);
 }  // namespace kolm
 
 #define KOLM_HIP_CHECK(x)                                              \

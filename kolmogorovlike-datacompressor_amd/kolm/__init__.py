@@ -35,10 +35,12 @@ from __future__ import annotations
 
 import struct
 import sys
+import zlib
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 from . import _lib
 from ._lib import KolmError, KolmUnavailable, KolmVerifyError  # noqa: F401
+from .checksums import Checksums, KolmChecksumError, as_checksums
 from .container import (MODE_CDC, MODE_FIXED, read_container, read_toc, uleb128_decode_stream,  # noqa: F401
                         uleb128_encode, write_container)
 from .decode import decode_block
@@ -50,6 +52,7 @@ __all__ = [
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
     "open_container", "Reader", "last_read", "last_dedup", "duplicate_blocks", "block_fingerprints",
+    "Checksums", "KolmChecksumError", "crc32_blocks", "crc32_combine", "last_checksums", "checksums_of", "check",
 ]
 
 CANDIDATE_NAMES = ["raw", "xor", "bbwt", "bbwt_bp", "bbwt_nib", "bbwt_br", "bbwt_gray", "lz77",
@@ -67,6 +70,9 @@ G_VERIFY: bool = False
 # dedup (not in PY): every device batch encodes its repeated blocks once and copies the payload
 # to the repeats; the output is byte for byte the same, the saving is time
 G_DEDUP: bool = False
+# checksums (not in PY): every device batch takes the CRC-32 of its blocks on the resident input;
+# the container's bytes do not change, the manifest is last_checksums() (kolm.checksums)
+G_CHECKSUMS: bool = False
 
 _last_stats: Dict[str, Any] = {}
 
@@ -114,6 +120,53 @@ def block_fingerprints(data: bytes, block_size: Optional[int] = None, bounds=Non
     """The device's 128-bit fingerprints of data's blocks, u64[nb, 2] (for tests: the function
     may change between versions and must not be persisted)."""
     return _lib.block_fingerprints(data, block_size, bounds, data_offset=data_offset)
+
+
+def _want_checksums(checksums: Optional[bool]) -> bool:
+    return G_CHECKSUMS if checksums is None else bool(checksums)
+
+
+_last_checksums: Optional[Checksums] = None
+
+
+def last_checksums() -> Optional[Checksums]:
+    """The manifest (kolm.checksums.Checksums) of the last encode call of this module when it
+    ran with checksums on: every block's CRC-32, taken on the device from the resident input,
+    and their combination, the CRC-32 of the whole input.  None when it ran with checksums off."""
+    return _last_checksums
+
+
+def _keep_checksums(want: bool, mode: int, size_field: int, data, lens, multi_block_size: Optional[int] = None) -> None:
+    """After an encode call: the manifest from the words the call left (kolm_ctx_checksums), or,
+    for a multi-device call (its contexts ignore the switch), from one crc32_blocks pass."""
+    global _last_checksums
+    _last_checksums = None
+    crcs = _lib.last_crcs()
+    if multi_block_size is not None and (want or _lib._ENV_CHECKSUMS):
+        crcs = crc32_blocks(data, multi_block_size)
+    if crcs is not None:
+        _last_checksums = Checksums(mode, size_field, len(data), lens, crcs)
+
+
+def _keep_empty(want: bool, mode: int, size_field: int) -> None:
+    """Empty input: nothing is launched; with checksums on the manifest is the empty one, not None."""
+    global _last_checksums
+    _last_checksums = Checksums(mode, size_field, 0, [], []) if want or _lib._ENV_CHECKSUMS else None
+
+
+def crc32_blocks(data: bytes, block_size: Optional[int] = None, bounds=None, data_offset: int = 0) -> List[int]:
+    """The standard CRC-32 (zlib.crc32) of data's blocks (fixed blocks of block_size, or
+    bounds[i]..bounds[i+1]; empty blocks are allowed and give 0), computed on the device
+    (k_crc32).  data_offset (0..15) places the data that many bytes into its device buffer."""
+    return _lib.crc32_blocks(data, block_size, bounds, data_offset=data_offset)
+
+
+def crc32_combine(a: int, b: int, len_b: int) -> int:
+    """CRC-32 of A + B from a = CRC-32(A), b = CRC-32(B) and len_b = len(B) (zlib's
+    crc32_combine; host arithmetic of the library, no device)."""
+    if len_b < 0:
+        raise ValueError("len_b must not be negative")
+    return _lib.crc32_combine(a, b, len_b)
 
 
 # ---------------------------------------------------------------------------
@@ -323,33 +376,38 @@ def candidate_mask(hot_path: bool = False, v2_new: Optional[bool] = None) -> int
 
 def encode_blocks(data: bytes, block_size: int, cand_mask: Optional[int] = None, devices: int = 1,
                   hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None,
-                  dedup: Optional[bool] = None):
+                  dedup: Optional[bool] = None, checksums: Optional[bool] = None):
     """Batched device MDL over fixed blocks: (method_ids, orig_lens, payloads, sizes).
     devices > 1 shards the blocks over that many GPUs of this process.  `verify` (default
     G_VERIFY): the payloads are decoded and compared with the input on the device before the
     call returns (KolmVerifyError otherwise).  `dedup` (default G_DEDUP): repeated blocks are
-    encoded once per device batch (same result; last_dedup())."""
+    encoded once per device batch (same result; last_dedup()).  `checksums` (default
+    G_CHECKSUMS): the blocks' CRC-32 are taken on the device from the resident input
+    (last_checksums(); with devices > 1 from one separate crc32_blocks pass)."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
-    global _last_stats
+    global _last_stats, _last_checksums
     mask = candidate_mask(hot_path, v2_new) if cand_mask is None else cand_mask
     n = len(data)
+    _last_checksums = None
     if n == 0:
+        _keep_empty(_want_checksums(checksums), MODE_FIXED, block_size)
         return [], [], [], None
     if devices > 1:
         sizes, method, payloads, st = _lib.encode_blocks_multi(bytes(data), block_size, devices, mask,
                                                                verify=_want_verify(verify), dedup=_want_dedup(dedup))
     else:
         sizes, method, payloads, st = _lib.encode_blocks(bytes(data), block_size, mask, verify=_want_verify(verify),
-                                                         dedup=_want_dedup(dedup))
+                                                         dedup=_want_dedup(dedup), checksums=_want_checksums(checksums))
     _last_stats = st
     orig = [min(block_size, n - i) for i in range(0, n, block_size)]
+    _keep_checksums(_want_checksums(checksums), MODE_FIXED, block_size, data, orig, block_size if devices > 1 else None)
     return [int(m) for m in method], orig, payloads, sizes
 
 
 def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1, hot_path: bool = False,
                           v2_new: Optional[bool] = None, verify: Optional[bool] = None,
-                          dedup: Optional[bool] = None) -> bytes:
+                          dedup: Optional[bool] = None, checksums: Optional[bool] = None) -> bytes:
     """Fixed-size chunking + per-block MDL selection + KOLR container (PY:2332-2445).
     `devices` (not in PY) spreads the blocks over that many GPUs of this process;
     `hot_path` (not in PY) restricts the candidates to ids 0..8; `v2_new` (default
@@ -357,50 +415,78 @@ def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1,
     G_VERIFY) checks on the device that every payload decodes to its block before the
     container is handed out (KolmVerifyError, and no container, otherwise; last_verify());
     `dedup` (not in PY, default G_DEDUP) encodes the repeated blocks of every device batch once
-    and copies the payload to the repeats: the same container in less time (last_dedup())."""
+    and copies the payload to the repeats: the same container in less time (last_dedup());
+    `checksums` (not in PY, default G_CHECKSUMS) takes the CRC-32 of every block on the device
+    from the resident input: the same container, and last_checksums() is its manifest (with
+    devices > 1 the manifest comes from one separate crc32_blocks pass over the data)."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
-    global _last_stats
+    global _last_stats, _last_checksums
+    _last_checksums = None
     n = len(data)
     nb = (n + block_size - 1) // block_size
     if nb > 0xFFFF:
         raise struct.error("'H' format requires 0 <= number <= 65535")
     if devices > 1:
         mids, orig, payloads, _ = encode_blocks(data, block_size, devices=devices, hot_path=hot_path, v2_new=v2_new,
-                                                verify=verify, dedup=dedup)
+                                                verify=verify, dedup=dedup, checksums=checksums)
         return write_container(MODE_FIXED, block_size, n, mids, orig, payloads)
     if n == 0:
+        _keep_empty(_want_checksums(checksums), MODE_FIXED, block_size)
         return write_container(MODE_FIXED, block_size, 0, [], [], [])
     # one native call: staged upload, batched encode, TOC, payloads into the container
     blob, st = _lib.compress_fixed(data, block_size, candidate_mask(hot_path, v2_new), verify=_want_verify(verify),
-                                   dedup=_want_dedup(dedup))
+                                   dedup=_want_dedup(dedup), checksums=_want_checksums(checksums))
     _last_stats = st
+    _keep_checksums(_want_checksums(checksums), MODE_FIXED, block_size, data,
+                    [min(block_size, n - i) for i in range(0, n, block_size)])
     return blob
 
 
 def compress_blocks_cdc(data: bytes, min_size: int = 4096, avg_size: int = 8192, max_size: int = 16384,
                         hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None,
-                        dedup: Optional[bool] = None) -> bytes:
+                        dedup: Optional[bool] = None, checksums: Optional[bool] = None) -> bytes:
     """FastCDC chunking + per-block MDL selection + KOLR container in CDC mode
     (PY:2213-2326): boundaries and every candidate on the GPU, one batched device call for
     all chunks (variable block geometry), the TOC on the host.  `hot_path` (not in PY)
-    restricts the candidates to ids 0..8; `verify` and `dedup` as in compress_blocks_fixed
-    (identical chunks are encoded once; this adds no shift resistance to the chunking)."""
-    global _last_stats
+    restricts the candidates to ids 0..8; `verify`, `dedup` and `checksums` as in
+    compress_blocks_fixed (identical chunks are encoded once; this adds no shift resistance to
+    the chunking)."""
+    global _last_stats, _last_checksums
+    _last_checksums = None
     bounds = cdc_fast_boundaries_strict(data, min_size, avg_size, max_size)
     if len(bounds) > 0xFFFF:  # PY packs the block count as '<H' before encoding (PY:2222)
         raise struct.error("'H' format requires 0 <= number <= 65535")
     n = len(data)
     if n == 0:
+        _keep_empty(_want_checksums(checksums), MODE_CDC, avg_size)
         return write_container(MODE_CDC, avg_size, 0, [], [], [])
     edges = [s for s, _ in bounds] + [n]
     _, method, payloads, st = _lib.encode_blocks_var(bytes(data), edges, candidate_mask(hot_path, v2_new),
-                                                     verify=_want_verify(verify), dedup=_want_dedup(dedup))
+                                                     verify=_want_verify(verify), dedup=_want_dedup(dedup),
+                                                     checksums=_want_checksums(checksums))
     _last_stats = st
+    _keep_checksums(_want_checksums(checksums), MODE_CDC, avg_size, data, [e - s for s, e in bounds])
     return write_container(MODE_CDC, avg_size, n, [int(m) for m in method], [e - s for s, e in bounds], payloads)
 
 
-def decompress(container: bytes, device: bool = True) -> bytes:
+def _match_toc(cs: Checksums, mode: int, size_field: int, total_len: int, orig) -> None:
+    """A manifest belongs to a container when mode, size_field, total_len and every block
+    length agree with its TOC."""
+    if (cs.mode, cs.size_field, cs.total_len) != (mode, size_field, total_len):
+        raise ValueError(f"checksums: the manifest is of another container (mode {cs.mode}, size field {cs.size_field}, "
+                         f"{cs.total_len} bytes; the container: mode {mode}, size field {size_field}, {total_len} bytes)")
+    if cs.lens != [int(n) for n in orig]:
+        raise ValueError("checksums: the manifest's block lengths differ from the container's")
+
+
+def _host_check(i: int, mid: int, want: int, block: bytes) -> None:
+    got = zlib.crc32(block)
+    if got != want:
+        raise KolmChecksumError(i, mid, want, got)
+
+
+def decompress(container: bytes, device: bool = True, checksums=None) -> bytes:
     """Inverse of compress_blocks_fixed / compress_blocks_cdc / the reference's containers
     (PY:2451-2550).  The TOC is parsed on the host; every block (ids 0..10: raw, xor, the
     BBWT family, lz77, lfsr_pred, Re-Pair and v2_new — KOLM_DECODE_MASK) is decoded on the GPU
@@ -408,8 +494,18 @@ def decompress(container: bytes, device: bool = True) -> bytes:
     kolm/decode.py take an id outside the device mask and an id-10 block whose header lists a
     Rice parameter above 15 (PY decodes any k byte; the device decodes 0..15, all that an
     encoder writes) or that is 2^28 bytes or longer (the device's id-10 limit); `device=False`
-    (not in PY) decodes everything on the host."""
+    (not in PY) decodes everything on the host.
+
+    `checksums` (not in PY): a kolm.checksums.Checksums manifest, or its sidecar bytes.  It must
+    agree with the TOC (mode, size field, total length, block lengths: ValueError otherwise).
+    The blocks decoded on the device are checked there, against their CRC-32, while the decoded
+    bytes are still resident (kolm_decode_blocks_crc); blocks the host decoders take are checked
+    with zlib.crc32.  A mismatch raises KolmChecksumError (a ValueError: .block .method
+    .expected .got) and no data is returned."""
     mode, size_field, total_len, mids, orig, payloads = read_container(container)
+    cs = None if checksums is None else as_checksums(checksums)
+    if cs is not None:
+        _match_toc(cs, mode, size_field, total_len, orig)
     parts: List[Optional[bytes]] = [None] * len(mids)
     if device:
         sel = [i for i, m in enumerate(mids)
@@ -418,7 +514,14 @@ def decompress(container: bytes, device: bool = True) -> bytes:
         if sel:
             try:
                 dec = _lib.decode_blocks([payloads[i] for i in sel], [mids[i] for i in sel],
-                                         [orig[i] for i in sel])
+                                         [orig[i] for i in sel],
+                                         None if cs is None else [cs.crcs[i] for i in sel])
+            except KolmChecksumError as e:  # numbered within the call: the container's block number
+                bad = sel[e.block]
+                for i in range(bad):  # the lowest-numbered bad block is named: host-decoded ones before it first
+                    if i not in sel:
+                        _host_check(i, mids[i], cs.crcs[i], decode_block(mids[i], payloads[i], orig[i]))
+                raise KolmChecksumError(bad, e.method, e.expected, e.got) from None
             except _lib.KolmError as e:
                 raise ValueError(str(e)) from None
             pos = 0
@@ -427,7 +530,11 @@ def decompress(container: bytes, device: bool = True) -> bytes:
                 pos += orig[i]
     out = bytearray()
     for i, (mid, n, p) in enumerate(zip(mids, orig, payloads)):
-        out += parts[i] if parts[i] is not None else decode_block(mid, p, n)
+        if parts[i] is None:
+            parts[i] = decode_block(mid, p, n)
+            if cs is not None:
+                _host_check(i, mid, cs.crcs[i], parts[i])
+        out += parts[i]
     if len(out) != total_len:
         raise ValueError(f"Length mismatch: got {len(out)}, expect {total_len}")
     return bytes(out)
@@ -452,13 +559,26 @@ class Reader:
     Blocks the device does not decode — a method id outside KOLM_DECODE_MASK, an id-10 block
     with a Rice parameter byte above 15 or of 2^28 bytes or more, the cases decompress() gives
     to the host decoders — are found at open; a call whose ranges touch one is served by
-    kolm.decode.decode_block on the host, for that call (same bytes; no speed claimed)."""
+    kolm.decode.decode_block on the host, for that call (same bytes; no speed claimed).
 
-    def __init__(self, container: bytes, ctx=None):
+    `checksums` (a kolm.checksums.Checksums or its sidecar bytes; it must agree with the TOC):
+    every read then takes the CRC-32 of the blocks it decodes, on the device where they lie
+    (kolm_reader_set_checksums) or with zlib.crc32 for host-decoded blocks, before any byte is
+    handed out: a mismatch raises KolmChecksumError and the read returns nothing."""
+
+    def __init__(self, container: bytes, ctx=None, checksums=None):
         blob = bytes(container)
+        self._cs = None if checksums is None else as_checksums(checksums)
         self._h, info = _lib.reader_open(blob, ctx)
         self.mode, self.size_field = info["mode"], info["size_field"]
         self._total = info["total_len"]
+        if self._cs is not None:
+            try:
+                _match_toc(self._cs, self.mode, self.size_field, self._total, info["orig_lens"])
+                _lib.reader_set_checksums(self._h, self._cs.crcs)
+            except Exception:
+                self.close()
+                raise
         starts, pos = [], 0
         for n in info["orig_lens"]:
             starts.append(pos)
@@ -536,6 +656,8 @@ class Reader:
                     if orig[b]:
                         if b not in dec:
                             dec[b] = decode_block(mids[b], payloads[b], orig[b])
+                            if self._cs is not None:
+                                _host_check(b, mids[b], self._cs.crcs[b], dec[b])
                         lo, hi = max(o, self._starts[b]), min(o + n, self._starts[b + 1])
                         piece += dec[b][lo - self._starts[b]:hi - self._starts[b]]
                     b += 1
@@ -592,10 +714,11 @@ class Reader:
         return offs
 
 
-def open_container(container: bytes, ctx=None) -> Reader:
+def open_container(container: bytes, ctx=None, checksums=None) -> Reader:
     """A Reader over `container` (see Reader).  ctx (optional): a context of kolm._lib.device_ctx
-    instead of the default one.  A malformed container raises what decompress raises."""
-    return Reader(container, ctx)
+    instead of the default one.  checksums (optional): the container's manifest; reads are then
+    checked.  A malformed container raises what decompress raises."""
+    return Reader(container, ctx, checksums)
 
 
 def verify(container: bytes, data: bytes) -> Dict[str, Any]:
@@ -616,3 +739,43 @@ def verify(container: bytes, data: bytes) -> Dict[str, Any]:
     return {"ok": rep["bad_blocks"] == 0 and rep["first_bad_reason"] == _lib.VR_NONE, "blocks": rep["blocks"],
             "bad": bad, "reason": rep["first_bad_reason"], "bytes": rep["bytes"],
             "ms_decode": rep["ms_decode"], "ms_compare": rep["ms_compare"]}
+
+
+def checksums_of(container: bytes) -> Checksums:
+    """The manifest of an existing container (one the reference wrote, for example): every block
+    is decoded on the device and its CRC-32 taken there (kolm_check_container without an
+    expectation); only the words come back.  Every method id must be in KOLM_DECODE_MASK; a
+    block the decoder rejects raises ValueError."""
+    mode, size_field, total_len, mids, orig, _, _ = read_toc(bytes(container))
+    got, rep = _lib.check_container(container, None)
+    if rep["bad_blocks"]:
+        raise ValueError(f"block {rep['first_bad_block']} (method {rep['first_bad_method']}): malformed payload")
+    return Checksums(mode, size_field, total_len, [int(n) for n in orig], got, rep["stream_crc"])
+
+
+def check(container: bytes, checksums) -> Dict[str, Any]:
+    """Is `container` intact?  Checked on the device without the original data
+    (kolm_check_container): the payloads go up, every block is decoded and its CRC-32 taken
+    there, and one word per block comes back to be compared with the manifest (a
+    kolm.checksums.Checksums or its sidecar bytes; ValueError when it is of another container).
+    Returns {"ok", "blocks", "bad": [(block, method, expected, got, reason), ...], "reason",
+    "stream_crc", "bytes", "ms_decode", "ms_crc"}: reason 1 the CRC-32 differs, 2 the decoder
+    rejected the payload (the reason of the lowest-numbered bad block at the top level).  A
+    malformed container raises the ValueError decompress raises; every method id must be in
+    KOLM_DECODE_MASK."""
+    cs = as_checksums(checksums)
+    mode, size_field, total_len, mids, orig, _, _ = read_toc(bytes(container))
+    _match_toc(cs, mode, size_field, total_len, orig)
+    got, rep = _lib.check_container(container, cs.crcs)
+    bad: List[Tuple[int, int, int, int, int]] = []
+    if rep["bad_blocks"]:
+        # the report names the lowest-numbered bad block with its reason (a rejected block is bad
+        # whatever its word); the others listed are the blocks whose words differ
+        for i, (w, g) in enumerate(zip(cs.crcs, got)):
+            if i == rep["first_bad_block"]:
+                bad.append((i, int(mids[i]), w, g, rep["first_bad_reason"]))
+            elif w != g:
+                bad.append((i, int(mids[i]), w, g, _lib.CR_MISMATCH))
+    return {"ok": rep["bad_blocks"] == 0, "blocks": rep["blocks"], "bad": bad, "reason": rep["first_bad_reason"],
+            "stream_crc": rep["stream_crc"], "bytes": rep["bytes"], "ms_decode": rep["ms_decode"],
+            "ms_crc": rep["ms_crc"]}

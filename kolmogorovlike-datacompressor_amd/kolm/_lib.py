@@ -13,11 +13,14 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+import re
 import sys
 import threading
 import time
 
 import numpy as np
+
+from .checksums import KolmChecksumError
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KOLM_LIB") or os.path.join(HERE, "libkolm_hip.so")  # KOLM_LIB: A/B builds
@@ -30,12 +33,14 @@ KOLM_REPAIR_MAX_BLOCK = 1 << 22
 KOLM_EFORMAT = -6
 KOLM_ERANGE = -7
 KOLM_EVERIFY = -8
+KOLM_ECHECKSUM = -9
 ERRORS = {-1: "bad argument", -2: "capacity too small", -3: "HIP error", -4: "collective error",
           -5: "not initialised", -6: "malformed container", -7: "field overflow",
-          -8: "payload does not decode to its input"}
+          -8: "payload does not decode to its input", -9: "decoded bytes do not match their CRC-32"}
 KOLM_VERIFY_EQUAL = 0xFFFFFFFF     # per-block word of the verify entry points: the block is equal
 KOLM_VERIFY_REJECTED = 0xFFFFFFFE  # the decoder rejected the payload
 VR_NONE, VR_DIFFER, VR_REJECTED, VR_LENGTH = 0, 1, 2, 3  # kolm_verify_report.first_bad_reason
+CR_NONE, CR_MISMATCH, CR_REJECTED = 0, 1, 2  # kolm_check_report.first_bad_reason
 
 
 class KolmUnavailable(ImportError):
@@ -112,6 +117,25 @@ class VerifyReport(ctypes.Structure):
         ("bytes", ctypes.c_uint64),
         ("ms_decode", ctypes.c_double),
         ("ms_compare", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class CheckReport(ctypes.Structure):
+    _fields_ = [
+        ("blocks", ctypes.c_uint32),
+        ("bad_blocks", ctypes.c_uint32),
+        ("first_bad_block", ctypes.c_uint32),
+        ("first_bad_method", ctypes.c_uint32),
+        ("first_bad_expected", ctypes.c_uint32),
+        ("first_bad_got", ctypes.c_uint32),
+        ("first_bad_reason", ctypes.c_uint32),
+        ("stream_crc", ctypes.c_uint32),
+        ("bytes", ctypes.c_uint64),
+        ("ms_decode", ctypes.c_double),
+        ("ms_crc", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -227,6 +251,14 @@ SIGNATURES = [
     ("kolm_block_fingerprints_device", I32, [P, P, P, U32, P]),
     ("kolm_find_duplicates_device", I32, [P, P, P, U32, P, ctypes.POINTER(DedupReport)]),
     ("kolm_dedup_plan", I32, [P, P, P, U32, U32, P, P, P, P, P, P, P, P, P]),
+    ("kolm_crc32_blocks_device", I32, [P, P, P, U32, P, ctypes.POINTER(ctypes.c_double)]),
+    ("kolm_crc32_combine", U32, [U32, U32, U64]),
+    ("kolm_ctx_set_checksums", I32, [P, I32]),
+    ("kolm_set_checksums", I32, [I32]),
+    ("kolm_ctx_checksums", I32, [P, P, U32, ctypes.POINTER(U32)]),
+    ("kolm_decode_blocks_crc", I32, [P, P, P, P, U32, P, U64, P, P]),
+    ("kolm_check_container", I32, [U8P, U64, P, P, U32, ctypes.POINTER(CheckReport)]),
+    ("kolm_reader_set_checksums", I32, [P, P, U32]),
 ]
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
@@ -234,9 +266,12 @@ KOLM_ERCCL = -4
 KOLM_DECODE_MASK = 0x7FF  # methods decoded on the device: every id 0..10 (kolm.h)
 
 
-def decode_blocks(payloads, methods, orig_lens) -> bytes:
+def decode_blocks(payloads, methods, orig_lens, expect=None) -> bytes:
     """Decode the given blocks on the device (kolm_decode_blocks); every method must be in
-    KOLM_DECODE_MASK.  Returns the concatenated decoded bytes."""
+    KOLM_DECODE_MASK.  Returns the concatenated decoded bytes.  expect (optional, one CRC-32
+    per block): kolm_decode_blocks_crc checks the decoded bytes on the device; a mismatch
+    raises KolmChecksumError for the lowest-numbered such block (numbered within this call)
+    and nothing is returned."""
     ensure_init()
     nb = len(payloads)
     if nb == 0:
@@ -248,8 +283,20 @@ def decode_blocks(payloads, methods, orig_lens) -> bytes:
     lens = np.ascontiguousarray(np.asarray(orig_lens, dtype=np.uint32))
     total = int(lens.astype(np.uint64).sum())
     out = np.zeros(max(total, 1), dtype=np.uint8)
-    check(load().kolm_decode_blocks(arena.ctypes.data, off.ctypes.data, meth.ctypes.data, lens.ctypes.data, nb,
-                                    out.ctypes.data, total))
+    if expect is None:
+        check(load().kolm_decode_blocks(arena.ctypes.data, off.ctypes.data, meth.ctypes.data, lens.ctypes.data, nb,
+                                        out.ctypes.data, total))
+        return out[:total].tobytes()
+    exp = np.ascontiguousarray(np.asarray(expect, dtype=np.uint32))
+    if exp.shape != (nb,):
+        raise ValueError("expect must have one CRC-32 per block")
+    got = np.zeros(nb, dtype=np.uint32)
+    rc = load().kolm_decode_blocks_crc(arena.ctypes.data, off.ctypes.data, meth.ctypes.data, lens.ctypes.data, nb,
+                                       out.ctypes.data, total, exp.ctypes.data, got.ctypes.data)
+    if rc == KOLM_ECHECKSUM:
+        i = int((got != exp).nonzero()[0][0])
+        raise KolmChecksumError(i, int(meth[i]), int(exp[i]), int(got[i]))
+    check(rc)
     return out[:total].tobytes()
 
 
@@ -387,24 +434,77 @@ class _dedup_scope:
         return False
 
 
+_last_crcs = None
+_ENV_CHECKSUMS = os.environ.get("KOLM_CHECKSUMS", "0").strip() not in ("", "0")  # the contexts' own default
+
+
+def ctx_checksums(ctx=None):
+    """The CRC-32 words of ctx's (None: the default context's) last encode call, container
+    block order (kolm_ctx_checksums): empty when that call ran with checksums off."""
+    n = U32(0)
+    check(load().kolm_ctx_checksums(ctx, None, 0, ctypes.byref(n)))
+    crc = np.zeros(max(n.value, 1), dtype=np.uint32)
+    check(load().kolm_ctx_checksums(ctx, crc.ctypes.data, len(crc), ctypes.byref(n)))
+    return [int(c) for c in crc[:n.value]]
+
+
+class _checksums_scope:
+    """Runs one native encode call with checksums on, on ctx (None: the default context), as
+    _dedup_scope does for dedup: the call's words are kept for last_crcs().  The caller holds
+    _result_lock (_encode_scope)."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+
+    def _set(self, on: int) -> int:
+        L = load()
+        return L.kolm_set_checksums(on) if self.ctx is None else L.kolm_ctx_set_checksums(self.ctx, on)
+
+    def __enter__(self):
+        check(self._set(1))
+        return self
+
+    def __exit__(self, et, ev, tb):
+        global _last_crcs
+        if et is None:
+            _last_crcs = ctx_checksums(self.ctx)
+        self._set(1 if _ENV_CHECKSUMS else 0)
+        return False
+
+
+def last_crcs():
+    """The CRC-32 words of the last encode call made through this binding, or None when it ran
+    with checksums off (or did not return a result)."""
+    return None if _last_crcs is None else list(_last_crcs)
+
+
 @contextlib.contextmanager
-def _encode_scope(verify: bool, dedup: bool, locked: bool = False, ctx=None):
-    """The switches of one native encode call.  dedup false: _verify_scope alone, the path as
-    it was (last_dedup() then reports nothing).  dedup true: _result_lock is taken once for
-    both switches (it is not reentrant), unless the caller holds it (locked).  With KOLM_DEDUP
-    set in the environment the contexts deduplicate whatever the argument says, so the call is
-    treated as dedup true and last_dedup() reports it."""
-    global _last_dedup
+def _encode_scope(verify: bool, dedup: bool, locked: bool = False, ctx=None, checksums: bool = False):
+    """The switches of one native encode call.  dedup and checksums false: _verify_scope alone,
+    the path as it was (last_dedup() then reports nothing, last_crcs() None).  Otherwise
+    _result_lock is taken once for all the switches (it is not reentrant), unless the caller holds
+    it (locked).  With KOLM_DEDUP / KOLM_CHECKSUMS set in the environment the contexts do it
+    whatever the argument says, so the call is treated as if the argument were true and
+    last_dedup() / last_crcs() report it."""
+    global _last_dedup, _last_crcs
     dedup = bool(dedup) or _ENV_DEDUP
+    checksums = bool(checksums) or _ENV_CHECKSUMS
+    _last_crcs = None
     if not dedup:
         _last_dedup = {}
+    if not dedup and not checksums:
         with _verify_scope(verify, locked, ctx):
             yield
         return
     if not locked:
         _result_lock.acquire()
     try:
-        with _dedup_scope(ctx), _verify_scope(verify, True, ctx):
+        with contextlib.ExitStack() as stack:
+            if checksums:
+                stack.enter_context(_checksums_scope(ctx))
+            if dedup:
+                stack.enter_context(_dedup_scope(ctx))
+            stack.enter_context(_verify_scope(verify, True, ctx))
             yield
     finally:
         if not locked:
@@ -477,6 +577,58 @@ def duplicate_blocks(data, block_size=None, bounds=None, device: int = None, dat
         return np.zeros(0, dtype=np.uint32), DedupReport().as_dict()
     b = _bounds_array(len(data), block_size, bounds)
     return _on_device(data, data_offset, device, lambda ctx, p: find_duplicates_device(ctx, p, b))
+
+
+def crc32_blocks_device(ctx, d_data: int, bounds):
+    """kolm_crc32_blocks_device: (the blocks' CRC-32 as a list, k_crc32's device ms)."""
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
+    nb = len(b) - 1
+    crc = np.zeros(max(nb, 1), dtype=np.uint32)
+    ms = ctypes.c_double(0.0)
+    check(load().kolm_crc32_blocks_device(ctx, d_data, b.ctypes.data, nb, crc.ctypes.data, ctypes.byref(ms)))
+    return [int(c) for c in crc[:nb]], ms.value
+
+
+def crc32_blocks(data, block_size=None, bounds=None, device: int = None, data_offset: int = 0):
+    """Uploads data and returns its blocks' CRC-32 (crc32_blocks_device).  bounds may hold
+    empty blocks (equal neighbours): their CRC-32 is 0."""
+    n = len(data)
+    if bounds is None:
+        if n == 0:
+            return []
+        b = _bounds_array(n, block_size, None)
+    else:
+        bl = [int(x) for x in bounds]
+        if not bl or bl[0] != 0 or bl[-1] != n or any(y < x for x, y in zip(bl, bl[1:])):
+            raise ValueError("bounds must start at 0, not decrease and end at len(data)")
+        b = np.ascontiguousarray(np.asarray(bl, dtype=np.uint64))
+    return _on_device(data, data_offset, device, lambda ctx, p: crc32_blocks_device(ctx, p, b))[0]
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """kolm_crc32_combine (host only, no device)."""
+    return int(load().kolm_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, int(len_b)))
+
+
+def check_container(container, expect=None):
+    """kolm_check_container on the default context: (the blocks' CRC-32 as computed from the
+    decoded bytes, report dict).  expect: one CRC-32 per block, or None to compute only.  A
+    malformed container raises ValueError as decompress does."""
+    ensure_init()
+    container = bytes(container)
+    got = np.zeros(65536, dtype=np.uint32)
+    exp = None
+    if expect is not None:  # a container holds at most 65535 blocks: the library never reads past the array
+        exp = np.zeros(65536, dtype=np.uint32)
+        exp[:len(expect)] = np.asarray(expect, dtype=np.uint32)[:65536]
+    rep = CheckReport()
+    rc = load().kolm_check_container(container, len(container), None if exp is None else exp.ctypes.data,
+                                     got.ctypes.data, len(got), ctypes.byref(rep))
+    if rc == KOLM_EFORMAT:
+        raise ValueError(load().kolm_last_error().decode())
+    check(rc)
+    r = rep.as_dict()
+    return [int(c) for c in got[:r["blocks"]]], r
 
 
 def dedup_plan(lens, fps, force=None, fp_bits: int = 128, differ=None, distinct_off=None) -> dict:
@@ -617,17 +769,19 @@ def device_ctx(device: int):
 
 
 def encode_blocks_device(ctx, d_data: int, n: int, block_size: int, d_arena: int, arena_cap: int,
-                         cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False, dedup: bool = False):
+                         cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False, dedup: bool = False,
+                         checksums: bool = False):
     """Batched MDL encode of fixed blocks of the device buffer d_data[0, n) into the
     device arena (kolm_encode_blocks_device).  Returns (sizes, method, offsets, stats).
     verify: the batch is checked on ctx before the call returns (KolmVerifyError).
-    dedup: repeated blocks are encoded once (same outputs; last_dedup())."""
+    dedup: repeated blocks are encoded once (same outputs; last_dedup()).
+    checksums: the blocks' CRC-32 are taken on the resident input (last_crcs())."""
     nb = (n + block_size - 1) // block_size if n else 0
     sizes = np.zeros((max(nb, 1), KOLM_NCAND), dtype=np.uint32)
     method = np.zeros(max(nb, 1), dtype=np.uint32)
     off = np.zeros(nb + 1, dtype=np.uint64)
     st = Stats()
-    with _encode_scope(verify, dedup, ctx=ctx):
+    with _encode_scope(verify, dedup, ctx=ctx, checksums=checksums):
         check(load().kolm_encode_blocks_device(ctx, d_data, n, block_size, cand_mask, None, d_arena, arena_cap,
                                                sizes.ctypes.data, method.ctypes.data, off.ctypes.data,
                                                ctypes.byref(st)), ctx)
@@ -761,10 +915,11 @@ def bbwt_mtf_rice(data: bytes, flags: int, k: int = 2) -> bytes:
 
 
 def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, force=None,
-                  verify: bool = False, dedup: bool = False):
+                  verify: bool = False, dedup: bool = False, checksums: bool = False):
     """Batched MDL encode of fixed-size blocks.  Returns (sizes[nb,KOLM_NCAND], method[nb],
     payloads list, stats dict).  verify: check the payloads on the device before returning
-    (KolmVerifyError on a bad block).  dedup: repeated blocks are encoded once."""
+    (KolmVerifyError on a bad block).  dedup: repeated blocks are encoded once.  checksums:
+    the blocks' CRC-32 are taken on the resident input (last_crcs())."""
     ensure_init()
     n = len(data)
     nb = (n + block_size - 1) // block_size if n else 0
@@ -783,7 +938,7 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MA
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    with _encode_scope(verify, dedup):
+    with _encode_scope(verify, dedup, checksums=checksums):
         check(load().kolm_encode_blocks(
             data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
             fz.ctypes.data if fz is not None else None,
@@ -794,10 +949,11 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MA
 
 
 def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False,
-                   dedup: bool = False):
+                   dedup: bool = False, checksums: bool = False):
     """The whole KOLR container of data in fixed blocks (kolm_compress_fixed): (bytes, stats).
     verify: every device batch is checked before its payloads count (KolmVerifyError, no
-    container, on a bad block).  dedup: every device batch encodes its repeated blocks once."""
+    container, on a bad block).  dedup: every device batch encodes its repeated blocks once.
+    checksums: every device batch takes its blocks' CRC-32 on the resident input (last_crcs())."""
     ensure_init()
     n = len(data)
     src = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8) if n else np.zeros(1, np.uint8)
@@ -808,7 +964,7 @@ def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, ve
     # copy out of it run under one lock (ctypes drops the GIL inside the call)
     with _result_lock:
         tc = time.perf_counter() if _HOST_PROF else 0.0
-        with _encode_scope(verify, dedup, locked=True):
+        with _encode_scope(verify, dedup, locked=True, checksums=checksums):
             rc = load().kolm_compress_fixed(src.ctypes.data, n, block_size, cand_mask, ctypes.byref(out),
                                             ctypes.byref(ln), ctypes.byref(st))
             if rc == KOLM_EVERIFY:
@@ -846,7 +1002,7 @@ def _new_bytes(n: int) -> bytes:
 
 
 def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, force=None, verify: bool = False,
-                      dedup: bool = False):
+                      dedup: bool = False, checksums: bool = False):
     """Batched MDL encode of content-defined blocks: block i = data[bounds[i]:bounds[i+1]]
     (bounds[0] = 0, strictly increasing, bounds[-1] = len(data)).  Same return value as
     encode_blocks."""
@@ -869,7 +1025,7 @@ def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, f
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    with _encode_scope(verify, dedup):
+    with _encode_scope(verify, dedup, checksums=checksums):
         check(load().kolm_encode_blocks(
             data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
             fz.ctypes.data if fz is not None else None,
@@ -994,9 +1150,29 @@ def reader_close(h):
     check(load().kolm_reader_close(h))
 
 
+def reader_set_checksums(h, crcs):
+    """kolm_reader_set_checksums: the expected CRC-32 of every block (None clears)."""
+    if crcs is None:
+        check(load().kolm_reader_set_checksums(h, None, 0))
+        return
+    c = np.ascontiguousarray(np.asarray(crcs, dtype=np.uint32))
+    rc = load().kolm_reader_set_checksums(h, c.ctypes.data, len(c))
+    if rc == -1:
+        raise ValueError(load().kolm_last_error().decode())
+    check(rc)
+
+
+_CHECKSUM_MSG = re.compile(r"block (\d+) \(method (\d+)\): expected CRC-32 ([0-9a-f]{8}), got ([0-9a-f]{8})")
+
+
 def _read_check(rc):
     if rc == -1:  # KOLM_EARG: a range outside the data, or a selected block that does not decode
         raise ValueError(load().kolm_last_error().decode())
+    if rc == KOLM_ECHECKSUM:  # the message names the block (kolm.h)
+        m = _CHECKSUM_MSG.search(load().kolm_last_error().decode())
+        if m:
+            raise KolmChecksumError(int(m.group(1)), int(m.group(2)), int(m.group(3), 16), int(m.group(4), 16))
+        raise KolmChecksumError(-1, -1, 0, 0)  # a text this binding does not know: still the checksum error
     check(rc)
 
 
