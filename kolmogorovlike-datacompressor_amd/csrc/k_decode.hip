@@ -2,10 +2,11 @@
 // block is independent, so a batch decodes one workgroup per block; inside a block the
 // reference's sequential loops are restated in parallel form:
 //   raw  (PY:2101)        copy.
-//   xor  (PY:2113-2122)   ULEB values < 256 (1 or 2 bytes): a byte starts a value iff the
-//   lfsr (PY:2005-2019)   previous byte is < 128 -> start flags + workgroup scan give each
+//   xor  (PY:2113-2122)   ULEB values of any width, used mod 256: a byte starts a value iff
+//   lfsr (PY:2005-2019)   the previous byte is < 128 -> start flags + workgroup scan give each
 //                         value's index; xor = running sum mod 256 (scan), lfsr = value +
 //                         LFSR state of the position (PY:1984-2003 table, taps 0x96, seed 1).
+//                         Exactly n values must fill the payload (PY ignores trailing bytes).
 //   lz77 (PY:1765-1812)   one thread per block parses the token stream (byte-aligned, the
 //                         only sequential part) into token records; the workgroup then
 //                         labels every output position with its token (max-scan of token
@@ -15,6 +16,7 @@
 // Errors (malformed payloads: lengths, distances, flags) set a per-block status word and
 // never read or write outside the block's payload / output range.
 #include "kolm_internal.h"
+#include "lz_parse_core.h"
 
 namespace kolm {
 
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(256) void k_dec_uleb(DecArgs a) {
     __syncthreads();
     u32 vcount = 0;  // values before this step
     u32 run = 0;     // xor: running sum (mod 256) before this step
-    bool bad = false;
+    const bool bad = plen && pay[plen - 1] >= 128;  // the payload ends inside a value
     for (u32 s0 = 0; s0 < plen; s0 += 2048) {
         const u32 j0 = s0 + tid * 8;
         u32 v[8];
@@ -83,10 +85,9 @@ __global__ __launch_bounds__(256) void k_dec_uleb(DecArgs a) {
             v[e] = 0xFFFFFFFFu;
             if (j < plen && (j == 0 || pay[j - 1] < 128)) {
                 u32 x = pay[j] & 0x7Fu;
-                if (pay[j] & 0x80u) {
-                    if (j + 1 >= plen || pay[j + 1] >= 2) bad = true;  // values are < 256
-                    else x |= (u32)pay[j + 1] << 7;
-                }
+                // only the value mod 256 counts: bit 7 comes from the second byte, the rest
+                // of a value of any width is skipped by the start flags
+                if ((pay[j] & 0x80u) && j + 1 < plen) x |= (u32)(pay[j + 1] & 1u) << 7;
                 v[e] = x;
                 ++nv;
                 sum += x;
@@ -112,24 +113,17 @@ __global__ __launch_bounds__(256) void k_dec_uleb(DecArgs a) {
         vcount += tot_v;
         run += tot_s;
     }
-    if (__syncthreads_or(bad) && tid == 0) a.status[b] = DEC_EFORMAT;
+    if (tid == 0 && bad) a.status[b] = DEC_EFORMAT;
     if (tid == 0 && vcount != n) a.status[b] = DEC_ELEN;
 }
 
 // ---------------------------------------------------------------- lz77
-__device__ inline bool uleb_get(const u8* p, u32 plen, u32& j, u32& v) {
-    v = 0;
-    for (u32 sh = 0; sh < 35; sh += 7) {
-        if (j >= plen) return false;
-        const u32 b = p[j++];
-        v |= (b & 0x7Fu) << sh;
-        if (!(b & 0x80u)) return true;
-    }
-    return false;
-}
-
-// One thread per block: token records (output start, length, literal byte | LIT or distance)
-// in the token slots [obase, obase + ntok) of the block; validation as PY:1765-1812.
+// One thread per block: the serial parse of csrc/lz_parse_core.h (validation as PY:1765-1812,
+// zero-length copies emit no record) into the block's own token slots [obase, obase + n):
+// records (output start, literal byte | LIT or distance), at most n of them, starts strictly
+// increasing.
+static_assert(lzp::LIT == LIT && lzp::OK == DEC_OK && lzp::ELEN == DEC_ELEN && lzp::EFORMAT == DEC_EFORMAT,
+              "lz_parse_core.h restates these");
 __global__ __launch_bounds__(64) void k_dec_lz_parse(DecArgs a, u32* tpos, u32* tval, u32* ntok) {
     const u32 li = blockIdx.x * 64 + threadIdx.x;
     if (li >= a.nlist) return;
@@ -137,36 +131,9 @@ __global__ __launch_bounds__(64) void k_dec_lz_parse(DecArgs a, u32* tpos, u32* 
     const u64 p0 = a.poff[b];
     const u32 plen = (u32)(a.poff[b + 1] - p0);
     const u32 o0 = a.obase[b], n = a.obase[b + 1] - o0;
-    const u8* p = a.pay + p0;
-    u32 j = 0, o = 0, t = 0, err = DEC_OK;
-    while (j < plen && o < n) {
-        const u32 flag = p[j++];
-        if (flag == 0) {
-            if (j >= plen) {
-                err = DEC_EFORMAT;
-                break;
-            }
-            tpos[o0 + t] = o;
-            tval[o0 + t] = LIT | p[j++];
-            ++t;
-            ++o;
-        } else if (flag == 1) {
-            u32 len, dist;
-            if (!uleb_get(p, plen, j, len) || !uleb_get(p, plen, j, dist) || dist == 0 || dist > min(o, 4096u)) {
-                err = DEC_EFORMAT;
-                break;
-            }
-            tpos[o0 + t] = o;
-            tval[o0 + t] = dist;
-            ++t;
-            o += min(len, n - o);  // PY truncates the last copy at orig_len
-        } else {
-            err = DEC_EFORMAT;
-            break;
-        }
-    }
-    if (err == DEC_OK && o != n) err = DEC_ELEN;
-    ntok[b] = err == DEC_OK ? t : 0u;
+    u32 nt = 0;
+    const u32 err = lzp::parse(a.pay + p0, plen, n, tpos + o0, tval + o0, &nt);
+    ntok[b] = nt;
     if (err != DEC_OK) a.status[b] = err;
 }
 

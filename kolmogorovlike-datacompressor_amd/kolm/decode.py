@@ -6,7 +6,10 @@ the reference block API and so that round trips can be tested.  They follow the
 reference decoders (PY = kolm_final_researched_v2-2.py), with one deliberate fix:
 PY's bit-plane decoder reads ``orig_len`` Rice values although the encoder emitted
 8*ceil(n/8); here the padded count is read so every container the
-reference encoder can produce decodes.
+reference encoder can produce decodes.  On streams no encoder writes they are pinned to PY
+by tests/golden/decode_cases.json; the two places where they reject what PY decodes (bytes
+after the n-th xor / lfsr value, a zero-length LZ77 copy from before the output's start) are
+listed in DESIGN.md §8.
 """
 from __future__ import annotations
 
@@ -24,12 +27,13 @@ def decode_raw(payload: bytes, n: int) -> bytes:  # PY:2101
 
 
 def _uleb_bytes(payload: bytes, n: int) -> np.ndarray:
-    """Decode n ULEB values < 2^14 (each 1 or 2 bytes)."""
+    """Decode n ULEB values of any width, each mod 256 (all that xor / lfsr use of them; PY
+    keeps the whole integer and masks the sum).  Exactly n values must fill the payload."""
     out = np.empty(n, dtype=np.int64)
     pos = 0
     for i in range(n):
         v, pos = uleb128_decode_stream(payload, pos)
-        out[i] = v
+        out[i] = v & 0xFF
     if pos != len(payload):
         raise ValueError("trailing bytes in ULEB stream")
     return out
@@ -132,7 +136,10 @@ def bbwt_inverse(L: bytes) -> bytes:  # PY:425-454
 
 def decode_bbwt_mtf_rice(payload: bytes, n: int, flags: int, k: int = 2) -> bytes:  # PY:2075-2089
     length = 8 * ((n + 7) // 8) if flags & 1 else n
-    seq = rice_decode(payload, k, length).astype(np.uint8)
+    seq = rice_decode(payload, k, length)
+    if seq.size and int(seq.max()) > 255:  # PY: bytes(seq) raises (a unary run of 64 or more)
+        raise ValueError("rice: value does not fit a byte")
+    seq = seq.astype(np.uint8)
     if flags & 16:
         g = seq.copy()
         g ^= g >> 1
