@@ -18,6 +18,7 @@
  *                             context per device).
  *   kolm_toc_write / kolm_toc_read: the KOLR container's header + TOC on the host
  *                             (PY:2375-2445 writer, PY:2451-2530 reader; kolm_toc.cpp).
+ *   kolm_find_device / kolm_reader_find: search of decoded bytes on the device (PY has none)
  *   kolm_reader_* / kolm_range_plan: random-access reads of a container (PY has no
  *                             equivalent: decompress, PY:2451-2550, decodes every block): only
  *                             the blocks a byte range touches are decoded, the ranges are packed
@@ -417,6 +418,65 @@ int kolm_reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens,
  * the ranges' bytes are written). */
 int kolm_reader_read_device(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges,
                             void* d_out, uint64_t out_cap, kolm_read_stats* stats);
+
+/* ---- search: where do byte strings occur in decoded data? ---------------------------------- */
+/* A call takes np patterns (1..KOLM_FIND_MAX_PATTERNS), pattern i = pats[pat_off[i], pat_off[i + 1])
+ * of 1..KOLM_FIND_MAX_LEN bytes, and a window [lo, hi) of the data.  (o, i) is a match iff
+ * lo <= o, o + len_i <= hi and data[o, o + len_i) == pattern i: every match counts, overlapping
+ * ones and those of identical patterns included.  The matches are listed in (offset, pattern
+ * index) order; with max_results the first max_results of that order.  counts [np] are the exact
+ * totals per pattern whatever max_results is.  Results are the same from run to run and do not
+ * depend on KOLM_READ_BYTES or KOLM_FIND_STAGE.
+ * On the device (csrc/find_core.h, k_find.hip): k_find_count (a workgroup per 4 KiB tile; a masked
+ * 64-bit compare of every position with every pattern's first 8 bytes, the rest only for
+ * candidates), a scan of the tile totals, one round trip for the totals, and k_find_emit writing
+ * (position, pattern) records at the scanned slots of a staging buffer of at most
+ * $KOLM_FIND_STAGE bytes (default 64 MiB, read per call, never less than one tile's records);
+ * a buffer with more matches is emitted in several launches over consecutive tile ranges.  No
+ * emit launch when nothing is to be returned (max_results = 0, or no match).
+ * KOLM_EARG before any launch, the message naming the pattern: np = 0 or np > 16, an empty pattern,
+ * a pattern of more than 256 bytes. */
+#define KOLM_FIND_MAX_PATTERNS 16
+#define KOLM_FIND_MAX_LEN 256
+/* The search of a resident buffer d_data[0, n) (device memory of any alignment, n < 2^31; the
+ * aligned 16-byte words that hold its first and last byte are read whole).  offs / which [cap]
+ * receive the first min(total, max_results) matches, nfound their number; which may be NULL when
+ * np == 1.  KOLM_ECAP when cap < min(total, max_results): counts are filled, nfound = the
+ * capacity needed, nothing is emitted.  ms (optional): device time of the kernels. */
+int kolm_find_device(kolm_ctx* ctx, const void* d_data, uint64_t n, const uint8_t* pats, const uint32_t* pat_off,
+                     uint32_t np, uint64_t max_results, uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap,
+                     uint64_t* nfound, double* ms);
+typedef struct kolm_find_stats {
+    uint32_t patterns;
+    uint32_t blocks_decoded;  /* blocks that hold a byte of the window */
+    uint32_t groups;          /* decode batches */
+    uint32_t emit_launches;   /* k_find_emit launches (0: a count-only call, or no match) */
+    uint64_t matches;         /* total over the patterns, whatever max_results is */
+    uint64_t returned;        /* min(matches, max_results) */
+    uint64_t bytes_decoded;
+    uint64_t bytes_scanned;   /* the groups' scan buffers: the window's bytes plus the carries */
+    double ms_decode;         /* device time of the decode kernels */
+    double ms_find;           /* device time of the search kernels */
+} kolm_find_stats;
+/* The search of the window [lo, hi) of a reader's decoded stream.  The blocks that hold a byte of
+ * the window are decoded group by group as kolm_reader_read decodes them (KOLM_READ_BYTES; payload
+ * runs compacted; a rejected payload: KOLM_EARG, block and method named; with
+ * kolm_reader_set_checksums in force every decoded block's CRC-32 is checked before any result
+ * leaves: KOLM_ECHECKSUM and no results).  Group g reports the matches that start in
+ * [S_g, S_g+1): S_0 = lo, S_g+1 = max(S_g, the group's end - (L - 1)) with L the longest pattern,
+ * hi after the last group; the bytes [S_g+1, group end), fewer than L, are copied in front of the
+ * next group's decoded bytes, so every start is examined once, in ascending order, and a match may
+ * span any number of blocks and groups.  The decoded bytes never leave the device; per group the
+ * totals make one round trip, and each emit launch one copy of its records.
+ * The result (absolute offsets, pattern indices) stays in the reader until its next find or its
+ * close: nfound entries, copied out by kolm_reader_find_copy (the two-call pattern of
+ * kolm_compress_fixed / kolm_result_copy).  KOLM_EARG before any launch also for lo > hi or
+ * hi > total_len and for a selected block the device does not decode (block and method named).
+ * stats optional. */
+int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, uint64_t lo, uint64_t hi,
+                     uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats);
+/* Results [first, first + n) of the reader's last find to offs / which (which optional). */
+int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint8_t* which);
 
 /* ---- dedup: encode repeated blocks once ---------------------------------------------- */
 /* A block's payload depends on its bytes, the candidate mask and its forced method and on

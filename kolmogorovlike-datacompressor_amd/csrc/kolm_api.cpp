@@ -3221,6 +3221,10 @@ struct kolm_reader {
     u8* dpay = nullptr;
     // the blocks' expected CRC-32 (kolm_reader_set_checksums): nb words, or empty = reads are not checked
     std::vector<u32> crcs;
+    // the result of the last kolm_reader_find: absolute offsets and pattern indices, in
+    // (offset, pattern) order (kolm_reader_find_copy)
+    std::vector<u64> f_offs;
+    std::vector<u8> f_which;
 };
 
 namespace {
@@ -3749,6 +3753,325 @@ int reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint
 }
 
 }  // namespace
+
+// ---- search of decoded bytes on the device (find_core.h, k_find.hip) ----
+namespace {
+
+u64 find_stage_bytes() {  // read per call, like KOLM_READ_BYTES
+    u64 v = fnd::STAGE_DEFAULT;
+    if (const char* e = getenv("KOLM_FIND_STAGE")) v = std::max<u64>(1, strtoull(e, nullptr, 10));
+    return v;
+}
+
+// np patterns, pattern i = pats[pat_off[i], pat_off[i + 1]); L = the longest
+int find_check_pats(const char* who, const uint8_t* pats, const uint32_t* pat_off, u32 np, u32* L) {
+    char msg[160];
+    if (np < 1 || np > KOLM_FIND_MAX_PATTERNS) {
+        snprintf(msg, sizeof msg, "%s: %u patterns (1..%u are allowed)", who, np, (u32)KOLM_FIND_MAX_PATTERNS);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    if (!pats || !pat_off) return KOLM_EARG;
+    *L = 0;
+    for (u32 i = 0; i < np; ++i) {
+        if (pat_off[i + 1] <= pat_off[i]) {
+            snprintf(msg, sizeof msg, "%s: pattern %u is empty", who, i);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        const u32 len = pat_off[i + 1] - pat_off[i];
+        if (len > KOLM_FIND_MAX_LEN) {
+            snprintf(msg, sizeof msg, "%s: pattern %u has %u bytes (at most %u)", who, i, len, (u32)KOLM_FIND_MAX_LEN);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        *L = std::max(*L, len);
+    }
+    return KOLM_OK;
+}
+
+const fnd::Pats* find_upload_pats(kolm_ctx* c, const uint8_t* pats, const uint32_t* pat_off, u32 np, fnd::Pats& hp) {
+    fnd::make_pats(pats, pat_off, np, hp);
+    fnd::Pats* dp = c->get<fnd::Pats>("fd_pats", 1);
+    KOLM_HIP_CHECK(hipMemcpyAsync(dp, &hp, sizeof hp, hipMemcpyHostToDevice, c->stream));
+    return dp;
+}
+
+// One scan buffer buf [0, n) on c->stream: count, scan, one round trip for the totals, then the
+// emit launches (none when nothing is to be returned).  counts [np] accumulate; (base + position,
+// pattern) are appended to offs / which until `limit` results are held.  more_than (optional):
+// when the group would return more than *more_than results, nothing is emitted and it is set to
+// that number.
+void find_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fnd::Pats* dP, u32 np, u64 base, u64 limit,
+                u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms,
+                u64* more_than = nullptr) {
+    const u32 ntiles = fnd::tiles(n);
+    if (!ntiles) return;
+    hipStream_t s = c->stream;
+    u32* cnt = c->get<u32>("fd_cnt", (size_t)(np + 1) * ntiles);
+    u64* tot = c->get<u64>("fd_tot", fnd::MAX_PATTERNS + 1);
+    u64* tscan = c->get<u64>("fd_scan", (size_t)ntiles + 1);
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_find_count", n);
+        launch_find_count(buf, n, lo, shi, dP, np, cnt, s);
+    }
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)(np + 1) * ntiles);
+        launch_find_scan(cnt, ntiles, np, tot, tscan, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
+    u64 htot[fnd::MAX_PATTERNS + 1] = {};
+    KOLM_HIP_CHECK(hipMemcpyAsync(htot, tot, sizeof(u64) * (np + 1), hipMemcpyDeviceToHost, s));
+    c->sync();
+    ms += ev_ms(c->ev[6], c->ev[7]);
+    for (u32 i = 0; i < np; ++i) counts[i] += htot[i];
+    const u64 total = htot[np];
+    const u64 want = std::min<u64>(total, limit > offs.size() ? limit - offs.size() : 0);
+    if (more_than && want > *more_than) {
+        *more_than = want;
+        return;
+    }
+    if (!want) return;
+    const u64 cap = std::min<u64>(fnd::stage_records(find_stage_bytes(), np), 0xFFFFFFFFull);
+    const u64 slots = std::min<u64>(cap, total);  // no launch holds more than either
+    u32* dpos = c->get<u32>("fd_pos", slots);
+    u8* dwhich = c->get<u8>("fd_which", slots);
+    // everything fits one launch and all of it is wanted: the tile scan stays on the device
+    const bool one = want == total && total <= cap;
+    std::vector<u64> hscan;
+    if (!one) {
+        hscan.resize((size_t)ntiles + 1);
+        KOLM_HIP_CHECK(hipMemcpyAsync(hscan.data(), tscan, sizeof(u64) * hscan.size(), hipMemcpyDeviceToHost, s));
+        c->sync();
+    }
+    std::vector<u32> hpos;
+    std::vector<u8> hwhich;
+    u64 got = 0;
+    for (u32 t0 = 0; got < want;) {
+        u32 t1 = ntiles;
+        u64 recs = total;
+        if (!one) {
+            while (hscan[t0 + 1] == hscan[t0]) ++t0;
+            t1 = fnd::emit_cut(hscan.data(), ntiles, t0, cap, want);
+            recs = hscan[t1] - hscan[t0];
+        }
+        KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
+        {
+            TScope t(c, KOLM_KT_EMIT, "k_find_emit", (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
+            launch_find_emit(buf, n, lo, shi, dP, np, t0, t1, tscan, dpos, dwhich, (u32)slots, s);
+        }
+        KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
+        const u64 take = std::min<u64>(recs, want - got);
+        hpos.resize(take), hwhich.resize(take);
+        KOLM_HIP_CHECK(hipMemcpyAsync(hpos.data(), dpos, sizeof(u32) * take, hipMemcpyDeviceToHost, s));
+        KOLM_HIP_CHECK(hipMemcpyAsync(hwhich.data(), dwhich, take, hipMemcpyDeviceToHost, s));
+        c->sync();
+        ms += ev_ms(c->ev[6], c->ev[7]);
+        for (u64 k = 0; k < take; ++k) offs.push_back(base + hpos[k]);
+        which.insert(which.end(), hwhich.begin(), hwhich.end());
+        got += take;
+        t0 = t1;
+        ++launches;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int kolm_find_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t* pats, const uint32_t* pat_off, uint32_t np,
+                     uint64_t max_results, uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap,
+                     uint64_t* nfound, double* ms) {
+    if (ms) *ms = 0.0;
+    if (nfound) *nfound = 0;
+    if (!c || !counts || !nfound) return KOLM_EARG;
+    u32 L = 0;
+    if (int rc = find_check_pats("kolm_find_device", pats, pat_off, np, &L)) return rc;
+    if (n >= (1ull << 31)) {
+        set_err("kolm_find_device: the buffer must be smaller than 2^31 bytes");
+        return KOLM_EARG;
+    }
+    if ((n && !d_data) || (cap && (!offs || (!which && np > 1)))) return KOLM_EARG;
+    for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    if (n == 0) return KOLM_OK;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        c->active = c->stream;
+        fnd::Pats hp;
+        const fnd::Pats* dP = find_upload_pats(c, pats, pat_off, np, hp);
+        std::vector<u64> o;
+        std::vector<u8> w;
+        u32 launches = 0;
+        double t = 0.0;
+        u64 more = cap;
+        find_group(c, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, dP, np, 0, max_results, counts, o, w, launches, t,
+                   &more);
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        if (ms) *ms = t;
+        if (more > cap) {
+            *nfound = more;
+            set_err("kolm_find_device: result capacity too small");
+            return KOLM_ECAP;
+        }
+        *nfound = o.size();
+        std::copy(o.begin(), o.end(), offs);
+        if (which) std::copy(w.begin(), w.end(), which);
+        return KOLM_OK;
+    });
+}
+
+int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, uint64_t lo, uint64_t hi,
+                     uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
+    if (stats) *stats = kolm_find_stats{};
+    if (nfound) *nfound = 0;
+    if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
+    // every argument check before the first launch: the patterns, the window, the selected blocks
+    u32 L = 0;
+    if (int rc = find_check_pats("kolm_reader_find", pats, pat_off, np, &L)) return rc;
+    if (lo > hi || hi > r->total) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "kolm_reader_find: the window [%llu, %llu) is not inside the container's %llu bytes",
+                 (unsigned long long)lo, (unsigned long long)hi, (unsigned long long)r->total);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    RangePlan p;
+    const u64 wlen = hi - lo;
+    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, &lo, &wlen, 1, 0, p)) return rc;
+    kolm_find_stats st{};
+    st.patterns = np;
+    st.blocks_decoded = (u32)p.sel.size();
+    st.groups = (u32)p.group_first.size() - 1;
+    for (u32 b : p.sel) {
+        const u32 m = r->methods[b];
+        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
+            r->lens[b] >= (1u << 31)) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        st.bytes_decoded += r->lens[b];
+    }
+    for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    kolm_ctx* c = r->c;
+    std::vector<u64> offs;
+    std::vector<u8> which;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->f_offs.clear(), r->f_which.clear();
+        if (p.sel.empty()) return KOLM_OK;
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        hipStream_t s = c->stream;
+        c->active = s;
+        fnd::Pats hp;
+        const fnd::Pats* dP = find_upload_pats(c, pats, pat_off, np, hp);
+        const bool checked = !r->crcs.empty();
+        u8* keep = c->get<u8>("fd_carry", fnd::MAX_LEN);  // the carry between two groups' scan buffers
+        std::vector<u32> gm, gl, status, scan, words;
+        std::vector<u64> gp;
+        std::vector<rng::Seg> runs;
+        u64 S = lo;
+        u32 carry = 0;
+        const u32 ng = (u32)p.group_first.size() - 1;
+        for (u32 g = 0; g < ng; ++g) {
+            const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
+            gm.resize(n), gl.resize(n), gp.assign((size_t)n + 1, 0);
+            runs.clear();
+            u64 tot = 0;
+            for (u32 i = i0; i < i1; ++i) {
+                const u32 b = p.sel[i];
+                gm[i - i0] = r->methods[b];
+                gl[i - i0] = r->lens[b];
+                tot += r->lens[b];
+                const u64 plen = r->poff[b + 1] - r->poff[b];
+                if (i == i0 || b != p.sel[i - 1] + 1) runs.push_back(rng::Seg{r->poff[b] - r->poff[0], gp[i - i0], 0});
+                runs.back().len += plen;
+                gp[i - i0 + 1] = gp[i - i0] + plen;
+            }
+            const u8* pay = r->dpay + runs[0].src;
+            const bool compact = runs.size() > 1;
+            if (compact) {  // as reads do: several payload runs are gathered first
+                u8* stage = c->get<u8>("rd_pay", gp[n] + 64);
+                gather_segments(c, "rd_c", r->dpay, stage, runs.data(), (u32)runs.size(), scan, c->ev[4], c->ev[5]);
+                pay = stage;
+            }
+            // the scan buffer: room for the carry (it ends at a 256-byte boundary), the group's
+            // decoded bytes there, padded as "rd_dec" is (the decoders' 64 bytes, the last aligned word)
+            u8* fb = c->get<u8>("fd_buf", fnd::MAX_LEN + tot + 64 + rng::WORD);
+            u8* dec = fb + fnd::MAX_LEN;
+            if (carry) KOLM_HIP_CHECK(hipMemcpyAsync(dec - carry, keep, carry, hipMemcpyDeviceToDevice, s));
+            double ms = 0.0;
+            if (int e = decode_batch(c, pay, gp.data(), gm.data(), gl.data(), n, tot, dec, &ms, &status)) return e;
+            st.ms_decode += ms;
+            for (u32 i = 0; i < n; ++i)
+                if (status[i]) {
+                    char msg[128];
+                    snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], gm[i],
+                             status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
+                    set_err(msg);
+                    return KOLM_EARG;
+                }
+            if (checked) {
+                words.resize(n);
+                crc_blocks_at(c, dec, gl.data(), n, words.data());
+                for (u32 i = 0; i < n; ++i) {
+                    const u32 b = p.sel[i0 + i];
+                    if (words[i] != r->crcs[b]) {
+                        checksum_message(b, gm[i], r->crcs[b], words[i]);
+                        return KOLM_ECHECKSUM;
+                    }
+                }
+            }
+            const u64 a = r->starts[p.sel[i0]], b = r->starts[p.sel[i1 - 1] + 1];
+            const fnd::GroupScan gs = fnd::group_scan(S, a, b, L, g + 1 == ng, hi);
+            st.bytes_scanned += gs.n;
+            find_group(c, dec - gs.carry, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which,
+                       st.emit_launches, st.ms_find);
+            S = gs.S_next;
+            carry = (u32)(b - S);  // < L: the bytes [S, b) end the scan buffer
+            if (g + 1 < ng && carry) {
+                KOLM_HIP_CHECK(hipMemcpyAsync(keep, dec + tot - carry, carry, hipMemcpyDeviceToDevice, s));
+                c->sync();  // the next group may move the scan buffer
+            }
+        }
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        return KOLM_OK;
+    });
+    if (rc) {  // no results leave a failed call
+        for (u32 i = 0; i < np; ++i) counts[i] = 0;
+        if (stats) *stats = st;
+        return rc;
+    }
+    for (u32 i = 0; i < np; ++i) st.matches += counts[i];
+    st.returned = offs.size();
+    *nfound = offs.size();
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->f_offs.swap(offs), r->f_which.swap(which);
+    }
+    if (stats) *stats = st;
+    return KOLM_OK;
+}
+
+int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint8_t* which) {
+    if (!r || !r->c) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(r->c->mu);
+    if (first > r->f_offs.size() || n > r->f_offs.size() - first) {
+        set_err("kolm_reader_find_copy: more results than the last find holds");
+        return KOLM_EARG;
+    }
+    if (n && !offs) return KOLM_EARG;
+    std::copy(r->f_offs.begin() + first, r->f_offs.begin() + first + n, offs);
+    if (which) std::copy(r->f_which.begin() + first, r->f_which.begin() + first + n, which);
+    return KOLM_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 

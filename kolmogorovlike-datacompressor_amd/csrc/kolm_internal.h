@@ -683,6 +683,20 @@ void dedup_expand(const std::vector<u32>& rep, const std::vector<u32>& distinct,
 void launch_crc32(const u8* text, const Geom& geo, const u32* scan, u64 nruns, const u32* tab, u32* raw, hipStream_t s);
 }  // namespace kolm
 
+// ---- k_find.hip: search of a resident buffer (find_core.h) ----
+#include "find_core.h"
+namespace kolm {
+// buf [0, n): the scan buffer (any alignment); a match is a position o with lo <= o < shi and
+// o + len <= n.  P: the call's patterns on the device.  cnt [(np + 1) * tiles(n)]: column i = the
+// tiles' counts of pattern i, column np = the tile totals.
+void launch_find_count(const u8* buf, u32 n, u32 lo, u32 shi, const fnd::Pats* P, u32 np, u32* cnt, hipStream_t s);
+// tot [np + 1]: the columns' sums; tscan [ntiles + 1]: exclusive scan of the tile totals
+void launch_find_scan(const u32* cnt, u32 ntiles, u32 np, u64* tot, u64* tscan, hipStream_t s);
+// the records of tiles [t0, t1) to out_pos / out_which [cap], the first at slot 0
+void launch_find_emit(const u8* buf, u32 n, u32 lo, u32 shi, const fnd::Pats* P, u32 np, u32 t0, u32 t1,
+                      const u64* tscan, u32* out_pos, u8* out_which, u32 cap, hipStream_t s);
+}  // namespace kolm
+
 #define KOLM_HIP_CHECK(x)                                              \
     do {                                                               \
         hipError_t e_ = (x);                                           \

@@ -51,7 +51,7 @@ __all__ = [
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
-    "open_container", "Reader", "last_read", "last_dedup", "duplicate_blocks", "block_fingerprints",
+    "open_container", "Reader", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
     "Checksums", "KolmChecksumError", "crc32_blocks", "crc32_combine", "last_checksums", "checksums_of", "check",
 ]
 
@@ -694,6 +694,62 @@ class Reader:
         n = self._total - offset if size is None or size < 0 else min(int(size), self._total - offset)
         return self.read_many([(offset, n)])[0]
 
+    def _search(self, patterns, start, end, limit):
+        """(offsets, pattern indices, counts) of the patterns in data[start:end]."""
+        global _last_find
+        h = self._handle()
+        pats = _lib.find_patterns(patterns)
+        start, end = int(start), self._total if end is None else int(end)
+        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
+            raise ValueError("start, end and limit must not be negative")
+        lo, hi = min(start, self._total), min(end, self._total)
+        if lo >= hi:  # nothing to search: no device call
+            return [], [], [0] * len(pats)
+        if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
+            data = self._read_host([(lo, hi - lo)])[0]
+            hits, counts = [], [0] * len(pats)
+            for i, p in enumerate(pats):
+                o = data.find(p)
+                while o >= 0:
+                    hits.append((lo + o, i))
+                    counts[i] += 1
+                    o = data.find(p, o + 1)
+            hits.sort()
+            if limit is not None:
+                hits = hits[:int(limit)]
+            rd = dict(_last_read)
+            _last_find = {"host": True, "patterns": len(pats), "matches": sum(counts), "returned": len(hits),
+                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
+                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
+                          "ms_find": 0.0}
+            return [o for o, _ in hits], [i for _, i in hits], counts
+        offs, which, counts = _lib.reader_find(h, pats, lo, hi, limit)
+        _last_find = {}
+        return offs, which, counts
+
+    def find(self, pattern, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None) -> List[int]:
+        """Every offset o with start <= o, o + len(pattern) <= end and data[o:o + len] ==
+        pattern, ascending, overlapping matches included; with `limit` the first `limit` of
+        them.  Searched on the device where the decoded blocks lie (kolm_reader_find): only
+        the offsets come back.  start / end are clipped to the data as slice bounds are
+        (negative values raise ValueError); the pattern is bytes-like, 1..256 bytes."""
+        return self._search([pattern], start, end, limit)[0]
+
+    def find_many(self, patterns, start: int = 0, end: Optional[int] = None,
+                  limit: Optional[int] = None) -> List[Tuple[int, int]]:
+        """(offset, pattern index) of every match of up to 16 patterns, sorted; identical
+        patterns are both reported."""
+        offs, which, _ = self._search(patterns, start, end, limit)
+        return list(zip(offs, which))
+
+    def count(self, pattern, start: int = 0, end: Optional[int] = None) -> int:
+        """len(find(pattern, start, end)) without listing the matches (no emit launch)."""
+        return self._search([pattern], start, end, 0)[2][0]
+
+    def count_many(self, patterns, start: int = 0, end: Optional[int] = None) -> List[int]:
+        """The number of matches of every pattern."""
+        return self._search(patterns, start, end, 0)[2]
+
     def read_many_device(self, ranges, dptr: int, cap: int) -> List[int]:
         """The ranges' bytes packed back to back at the device address dptr (cap bytes
         available), left on the device; returns every range's offset in that buffer.  Ranges
@@ -712,6 +768,24 @@ class Reader:
             offs.append(pos)
             pos += n
         return offs
+
+
+def last_find() -> Dict[str, Any]:
+    """kolm_find_stats of the last Reader.find / find_many / count / count_many: patterns,
+    matches (total, whatever the limit), returned, blocks_decoded, groups, emit_launches,
+    bytes_decoded, bytes_scanned, ms_decode, ms_find (a call served on the host reports its
+    blocks and matches with groups = 0 and "host": True)."""
+    return dict(_last_find) if _last_find.get("host") else _lib.last_find()
+
+
+_last_find: Dict[str, Any] = {}
+
+
+def find(container: bytes, pattern, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None,
+         checksums=None) -> List[int]:
+    """Reader.find over `container`: opens, searches, closes."""
+    with Reader(container, checksums=checksums) as r:
+        return r.find(pattern, start, end, limit)
 
 
 def open_container(container: bytes, ctx=None, checksums=None) -> Reader:

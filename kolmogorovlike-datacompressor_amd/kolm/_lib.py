@@ -158,6 +158,24 @@ class ReadStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FindStats(ctypes.Structure):
+    _fields_ = [
+        ("patterns", ctypes.c_uint32),
+        ("blocks_decoded", ctypes.c_uint32),
+        ("groups", ctypes.c_uint32),
+        ("emit_launches", ctypes.c_uint32),
+        ("matches", ctypes.c_uint64),
+        ("returned", ctypes.c_uint64),
+        ("bytes_decoded", ctypes.c_uint64),
+        ("bytes_scanned", ctypes.c_uint64),
+        ("ms_decode", ctypes.c_double),
+        ("ms_find", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RangeSeg(ctypes.Structure):
     _fields_ = [("src", ctypes.c_uint64), ("dst", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
@@ -259,7 +277,13 @@ SIGNATURES = [
     ("kolm_decode_blocks_crc", I32, [P, P, P, P, U32, P, U64, P, P]),
     ("kolm_check_container", I32, [U8P, U64, P, P, U32, ctypes.POINTER(CheckReport)]),
     ("kolm_reader_set_checksums", I32, [P, P, U32]),
+    ("kolm_find_device", I32, [P, P, U64, P, P, U32, U64, P, P, P, U64, ctypes.POINTER(U64),
+                               ctypes.POINTER(ctypes.c_double)]),
+    ("kolm_reader_find", I32, [P, P, P, U32, U64, U64, U64, P, ctypes.POINTER(U64), ctypes.POINTER(FindStats)]),
+    ("kolm_reader_find_copy", I32, [P, U64, U64, P, P]),
 ]
+KOLM_FIND_MAX_PATTERNS = 16
+KOLM_FIND_MAX_LEN = 256
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
 KOLM_ERCCL = -4
@@ -1188,6 +1212,91 @@ def reader_read(h, ranges) -> bytes:
                                         total, ctypes.byref(st)))
     _last_read = st.as_dict()
     return out
+
+
+# ---- search (kolm_find_device, kolm_reader_find) -------------------------------------------
+
+NO_LIMIT = (1 << 64) - 1
+_last_find: dict = {}
+
+
+def last_find() -> dict:
+    """kolm_find_stats of the last search made through this binding."""
+    return dict(_last_find)
+
+
+def find_patterns(patterns) -> list:
+    """The patterns of a search as a list of bytes; ValueError for what the library refuses
+    (no pattern or more than 16, an empty one, one of more than 256 bytes)."""
+    if isinstance(patterns, (bytes, bytearray, memoryview, str)):
+        raise TypeError("patterns must be a sequence of bytes-like objects")
+    pats = [memoryview(p).tobytes() for p in patterns]
+    if not 1 <= len(pats) <= KOLM_FIND_MAX_PATTERNS:
+        raise ValueError(f"{len(pats)} patterns (1..{KOLM_FIND_MAX_PATTERNS} are allowed)")
+    for i, p in enumerate(pats):
+        if not p:
+            raise ValueError(f"pattern {i} is empty")
+        if len(p) > KOLM_FIND_MAX_LEN:
+            raise ValueError(f"pattern {i} has {len(p)} bytes (at most {KOLM_FIND_MAX_LEN})")
+    return pats
+
+
+def _pattern_arrays(pats):
+    off = np.zeros(len(pats) + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(p) for p in pats])
+    flat = np.frombuffer(b"".join(bytes(p) for p in pats) + b"\0", dtype=np.uint8)
+    return flat, off
+
+
+def find_device(ctx, dptr: int, n: int, patterns, limit=None):
+    """kolm_find_device over the n bytes at the device address dptr.  Returns (offsets,
+    pattern indices, counts per pattern, device ms); the patterns are passed as given (the
+    library's argument errors raise ValueError)."""
+    pats = list(patterns)
+    flat, off = _pattern_arrays(pats)
+    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
+    nfound, ms = U64(0), ctypes.c_double(0.0)
+    lim = NO_LIMIT if limit is None else int(limit)
+    L = load()
+    rc = L.kolm_find_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim, counts.ctypes.data, None,
+                            None, 0, ctypes.byref(nfound), ctypes.byref(ms))
+    if rc == -1:
+        raise ValueError(L.kolm_last_error().decode())
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint8)
+    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
+        rc = L.kolm_find_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim, counts.ctypes.data,
+                                offs.ctypes.data, which.ctypes.data, k, ctypes.byref(nfound), ctypes.byref(ms))
+    check(rc)
+    k = int(nfound.value)
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]], ms.value
+
+
+def find_bytes(data, patterns, limit=None, device: int = None, data_offset: int = 0):
+    """Uploads data data_offset (0..15) bytes into a buffer and searches it (find_device)."""
+    return _on_device(data, data_offset, device, lambda ctx, p: find_device(ctx, p, len(data), patterns, limit))
+
+
+def reader_find(h, patterns, lo: int, hi: int, limit=None):
+    """kolm_reader_find + kolm_reader_find_copy.  Returns (offsets, pattern indices, counts per
+    pattern); the stats go to last_find().  Argument errors raise ValueError, a checksum
+    mismatch KolmChecksumError, and last_find() keeps what it held."""
+    global _last_find
+    pats = list(patterns)
+    flat, off = _pattern_arrays(pats)
+    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
+    nfound = U64(0)
+    st = FindStats()
+    lim = NO_LIMIT if limit is None else int(limit)
+    _read_check(load().kolm_reader_find(h, flat.ctypes.data, off.ctypes.data, len(pats), lo, hi, lim, counts.ctypes.data,
+                                        ctypes.byref(nfound), ctypes.byref(st)))
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint8)
+    check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
+    _last_find = st.as_dict()
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]]
 
 
 def reader_read_device(h, ranges, dptr: int, cap: int):
