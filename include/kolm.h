@@ -19,6 +19,8 @@
  *   kolm_toc_write / kolm_toc_read: the KOLR container's header + TOC on the host
  *                             (PY:2375-2445 writer, PY:2451-2530 reader; kolm_toc.cpp).
  *   kolm_find_device / kolm_reader_find: search of decoded bytes on the device (PY has none)
+ *   kolm_patset_create / kolm_find_set_device / kolm_reader_find_set: the same for a prepared set of
+ *     up to 65 536 patterns in one pass (PY has none)
  *   kolm_reader_* / kolm_range_plan: random-access reads of a container (PY has no
  *                             equivalent: decompress, PY:2451-2550, decodes every block): only
  *                             the blocks a byte range touches are decoded, the ranges are packed
@@ -477,6 +479,51 @@ int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_of
                      uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats);
 /* Results [first, first + n) of the reader's last find to offs / which (which optional). */
 int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint8_t* which);
+
+/* ---- pattern sets: up to 65 536 patterns in one pass ----------------------------------------- */
+/* A set holds np patterns (1..KOLM_FIND_SET_MAX_PATTERNS) of 1..KOLM_FIND_MAX_LEN bytes each,
+ * pairwise distinct: two equal patterns are refused with KOLM_EARG, the message naming both
+ * indices.  The match rule, the order of the results, the exact per-pattern totals and the
+ * independence of KOLM_READ_BYTES / KOLM_FIND_STAGE are those of the search above; distinctness
+ * bounds the matches of one position (prefixes of one another: at most min(np, 256)).
+ * On the device (csrc/findset_core.h, k_findset.hip): the key of a pattern is its first
+ * K = min(8, shortest pattern) bytes; the patterns of one key form a bucket (ascending index) behind
+ * an open-addressing table of the keys and a bitmap filter of 1..32 KiB that the kernels keep in
+ * LDS.  k_findset_count tests each position's key against the filter, probes the table on a hit and
+ * verifies the bucket's patterns in full; the cost of a position does not grow with the set while
+ * few positions pass the filter.  Scan, round trip, staging (8-byte records) and emit launches as
+ * above.  A set owns its device tables and is bound to the context it was made in (NULL: the
+ * default context); it is used with readers and buffers of that context and must be freed before
+ * that context is destroyed.  The per-pattern counters of a call live in the set: calls that use
+ * one set are serialised by its context's lock, and a set is shared between threads only that way. */
+#define KOLM_FIND_SET_MAX_PATTERNS 65536
+typedef struct kolm_patset kolm_patset;
+typedef struct kolm_patset_info_t {
+    uint32_t np;              /* patterns */
+    uint32_t key_bytes;       /* K */
+    uint32_t keys;            /* distinct keys = buckets */
+    uint32_t slots;           /* of the key table: a power of two >= 2 * keys */
+    uint32_t filter_bits;     /* a power of two >= 16 * keys within [2^13, 2^18] */
+    uint32_t longest;         /* L, the longest pattern: the hold-back between decode groups */
+    uint32_t longest_bucket;  /* patterns that share one key, at most (they are verified one by one) */
+} kolm_patset_info_t;
+int kolm_patset_create(kolm_ctx* ctx, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, kolm_patset** out);
+void kolm_patset_free(kolm_patset* ps);
+int kolm_patset_info(const kolm_patset* ps, kolm_patset_info_t* out);
+/* kolm_find_device for a set: counts [np] may be NULL; which holds 32-bit pattern indices.
+ * KOLM_ECAP as there (counts filled, nfound = the capacity needed, nothing emitted). */
+int kolm_find_set_device(kolm_ctx* ctx, const void* d_data, uint64_t n, const kolm_patset* ps, uint64_t max_results,
+                         uint64_t* counts, uint64_t* offs, uint32_t* which, uint64_t cap, uint64_t* nfound, double* ms);
+/* kolm_reader_find for a set: one decode of the window's blocks serves the whole set (the hold-back
+ * uses the set's longest pattern).  counts [np] may be NULL.  The per-pattern counters are zeroed
+ * once per call and read back once at its end; per group only the grand total makes the round
+ * trip.  KOLM_EARG before any launch also for a set of another context than the reader's.  The
+ * result stays in the reader until its next find / find_set or its close and is copied out by
+ * kolm_reader_find_copy32; stats->patterns = np. */
+int kolm_reader_find_set(kolm_reader* r, const kolm_patset* ps, uint64_t lo, uint64_t hi, uint64_t max_results,
+                         uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats);
+/* Results [first, first + n) of the reader's last find_set to offs / which (which optional). */
+int kolm_reader_find_copy32(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint32_t* which);
 
 /* ---- dedup: encode repeated blocks once ---------------------------------------------- */
 /* A block's payload depends on its bytes, the candidate mask and its forced method and on

@@ -3225,6 +3225,10 @@ struct kolm_reader {
     // (offset, pattern) order (kolm_reader_find_copy)
     std::vector<u64> f_offs;
     std::vector<u8> f_which;
+    // the result of the last kolm_reader_find_set (kolm_reader_find_copy32); either call empties
+    // the other's result
+    std::vector<u64> fs_offs;
+    std::vector<u32> fs_which;
 };
 
 namespace {
@@ -3876,6 +3880,114 @@ void find_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fnd::P
     }
 }
 
+// The checks of a reader's search that precede every launch: the window, and that the device
+// decodes every block that holds a byte of it.  Fills the plan and the stats' block figures.
+int find_plan(const char* who, kolm_reader* r, u64 lo, u64 hi, RangePlan& p, kolm_find_stats& st) {
+    if (lo > hi || hi > r->total) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: the window [%llu, %llu) is not inside the container's %llu bytes", who,
+                 (unsigned long long)lo, (unsigned long long)hi, (unsigned long long)r->total);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    const u64 wlen = hi - lo;
+    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, &lo, &wlen, 1, 0, p)) return rc;
+    st.blocks_decoded = (u32)p.sel.size();
+    st.groups = (u32)p.group_first.size() - 1;
+    for (u32 b : p.sel) {
+        const u32 m = r->methods[b];
+        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
+            r->lens[b] >= (1u << 31)) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        st.bytes_decoded += r->lens[b];
+    }
+    return KOLM_OK;
+}
+
+// The group loop of a reader's search (the caller holds the context's lock and has selected the
+// device): the plan's blocks are decoded group by group -- payload runs, compaction, decode_batch,
+// status and checksum checks -- each group's bytes behind the carry of the groups before it, and
+// search(scan buffer, its fnd::GroupScan) runs on every scan buffer in stream order.  L: the
+// longest pattern (the hold-back).
+template <class F>
+int find_over_groups(kolm_reader* r, const RangePlan& p, u64 lo, u64 hi, u32 L, kolm_find_stats& st, F&& search) {
+    kolm_ctx* c = r->c;
+    hipStream_t s = c->stream;
+    const bool checked = !r->crcs.empty();
+    u8* keep = c->get<u8>("fd_carry", fnd::MAX_LEN);  // the carry between two groups' scan buffers
+    std::vector<u32> gm, gl, status, scan, words;
+    std::vector<u64> gp;
+    std::vector<rng::Seg> runs;
+    u64 S = lo;
+    u32 carry = 0;
+    const u32 ng = (u32)p.group_first.size() - 1;
+    for (u32 g = 0; g < ng; ++g) {
+        const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
+        gm.resize(n), gl.resize(n), gp.assign((size_t)n + 1, 0);
+        runs.clear();
+        u64 tot = 0;
+        for (u32 i = i0; i < i1; ++i) {
+            const u32 b = p.sel[i];
+            gm[i - i0] = r->methods[b];
+            gl[i - i0] = r->lens[b];
+            tot += r->lens[b];
+            const u64 plen = r->poff[b + 1] - r->poff[b];
+            if (i == i0 || b != p.sel[i - 1] + 1) runs.push_back(rng::Seg{r->poff[b] - r->poff[0], gp[i - i0], 0});
+            runs.back().len += plen;
+            gp[i - i0 + 1] = gp[i - i0] + plen;
+        }
+        const u8* pay = r->dpay + runs[0].src;
+        const bool compact = runs.size() > 1;
+        if (compact) {  // as reads do: several payload runs are gathered first
+            u8* stage = c->get<u8>("rd_pay", gp[n] + 64);
+            gather_segments(c, "rd_c", r->dpay, stage, runs.data(), (u32)runs.size(), scan, c->ev[4], c->ev[5]);
+            pay = stage;
+        }
+        // the scan buffer: room for the carry (it ends at a 256-byte boundary), the group's
+        // decoded bytes there, padded as "rd_dec" is (the decoders' 64 bytes, the last aligned word)
+        u8* fb = c->get<u8>("fd_buf", fnd::MAX_LEN + tot + 64 + rng::WORD);
+        u8* dec = fb + fnd::MAX_LEN;
+        if (carry) KOLM_HIP_CHECK(hipMemcpyAsync(dec - carry, keep, carry, hipMemcpyDeviceToDevice, s));
+        double ms = 0.0;
+        if (int e = decode_batch(c, pay, gp.data(), gm.data(), gl.data(), n, tot, dec, &ms, &status)) return e;
+        st.ms_decode += ms;
+        for (u32 i = 0; i < n; ++i)
+            if (status[i]) {
+                char msg[128];
+                snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], gm[i],
+                         status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
+                set_err(msg);
+                return KOLM_EARG;
+            }
+        if (checked) {
+            words.resize(n);
+            crc_blocks_at(c, dec, gl.data(), n, words.data());
+            for (u32 i = 0; i < n; ++i) {
+                const u32 b = p.sel[i0 + i];
+                if (words[i] != r->crcs[b]) {
+                    checksum_message(b, gm[i], r->crcs[b], words[i]);
+                    return KOLM_ECHECKSUM;
+                }
+            }
+        }
+        const u64 a = r->starts[p.sel[i0]], b = r->starts[p.sel[i1 - 1] + 1];
+        const fnd::GroupScan gs = fnd::group_scan(S, a, b, L, g + 1 == ng, hi);
+        st.bytes_scanned += gs.n;
+        search(dec - gs.carry, gs);
+        S = gs.S_next;
+        carry = (u32)(b - S);  // < L: the bytes [S, b) end the scan buffer
+        if (g + 1 < ng && carry) {
+            KOLM_HIP_CHECK(hipMemcpyAsync(keep, dec + tot - carry, carry, hipMemcpyDeviceToDevice, s));
+            c->sync();  // the next group may move the scan buffer
+        }
+    }
+    return KOLM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3931,38 +4043,17 @@ int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_of
     // every argument check before the first launch: the patterns, the window, the selected blocks
     u32 L = 0;
     if (int rc = find_check_pats("kolm_reader_find", pats, pat_off, np, &L)) return rc;
-    if (lo > hi || hi > r->total) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "kolm_reader_find: the window [%llu, %llu) is not inside the container's %llu bytes",
-                 (unsigned long long)lo, (unsigned long long)hi, (unsigned long long)r->total);
-        set_err(msg);
-        return KOLM_EARG;
-    }
     RangePlan p;
-    const u64 wlen = hi - lo;
-    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, &lo, &wlen, 1, 0, p)) return rc;
     kolm_find_stats st{};
     st.patterns = np;
-    st.blocks_decoded = (u32)p.sel.size();
-    st.groups = (u32)p.group_first.size() - 1;
-    for (u32 b : p.sel) {
-        const u32 m = r->methods[b];
-        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
-            r->lens[b] >= (1u << 31)) {
-            char msg[128];
-            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        st.bytes_decoded += r->lens[b];
-    }
+    if (int rc = find_plan("kolm_reader_find", r, lo, hi, p, st)) return rc;
     for (u32 i = 0; i < np; ++i) counts[i] = 0;
     kolm_ctx* c = r->c;
     std::vector<u64> offs;
     std::vector<u8> which;
     int rc = guarded([&] {
         std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.clear(), r->f_which.clear();
+        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
         if (p.sel.empty()) return KOLM_OK;
         KOLM_HIP_CHECK(hipSetDevice(c->device));
         c->timing_reset();
@@ -3970,75 +4061,11 @@ int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_of
         c->active = s;
         fnd::Pats hp;
         const fnd::Pats* dP = find_upload_pats(c, pats, pat_off, np, hp);
-        const bool checked = !r->crcs.empty();
-        u8* keep = c->get<u8>("fd_carry", fnd::MAX_LEN);  // the carry between two groups' scan buffers
-        std::vector<u32> gm, gl, status, scan, words;
-        std::vector<u64> gp;
-        std::vector<rng::Seg> runs;
-        u64 S = lo;
-        u32 carry = 0;
-        const u32 ng = (u32)p.group_first.size() - 1;
-        for (u32 g = 0; g < ng; ++g) {
-            const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
-            gm.resize(n), gl.resize(n), gp.assign((size_t)n + 1, 0);
-            runs.clear();
-            u64 tot = 0;
-            for (u32 i = i0; i < i1; ++i) {
-                const u32 b = p.sel[i];
-                gm[i - i0] = r->methods[b];
-                gl[i - i0] = r->lens[b];
-                tot += r->lens[b];
-                const u64 plen = r->poff[b + 1] - r->poff[b];
-                if (i == i0 || b != p.sel[i - 1] + 1) runs.push_back(rng::Seg{r->poff[b] - r->poff[0], gp[i - i0], 0});
-                runs.back().len += plen;
-                gp[i - i0 + 1] = gp[i - i0] + plen;
-            }
-            const u8* pay = r->dpay + runs[0].src;
-            const bool compact = runs.size() > 1;
-            if (compact) {  // as reads do: several payload runs are gathered first
-                u8* stage = c->get<u8>("rd_pay", gp[n] + 64);
-                gather_segments(c, "rd_c", r->dpay, stage, runs.data(), (u32)runs.size(), scan, c->ev[4], c->ev[5]);
-                pay = stage;
-            }
-            // the scan buffer: room for the carry (it ends at a 256-byte boundary), the group's
-            // decoded bytes there, padded as "rd_dec" is (the decoders' 64 bytes, the last aligned word)
-            u8* fb = c->get<u8>("fd_buf", fnd::MAX_LEN + tot + 64 + rng::WORD);
-            u8* dec = fb + fnd::MAX_LEN;
-            if (carry) KOLM_HIP_CHECK(hipMemcpyAsync(dec - carry, keep, carry, hipMemcpyDeviceToDevice, s));
-            double ms = 0.0;
-            if (int e = decode_batch(c, pay, gp.data(), gm.data(), gl.data(), n, tot, dec, &ms, &status)) return e;
-            st.ms_decode += ms;
-            for (u32 i = 0; i < n; ++i)
-                if (status[i]) {
-                    char msg[128];
-                    snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], gm[i],
-                             status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
-                    set_err(msg);
-                    return KOLM_EARG;
-                }
-            if (checked) {
-                words.resize(n);
-                crc_blocks_at(c, dec, gl.data(), n, words.data());
-                for (u32 i = 0; i < n; ++i) {
-                    const u32 b = p.sel[i0 + i];
-                    if (words[i] != r->crcs[b]) {
-                        checksum_message(b, gm[i], r->crcs[b], words[i]);
-                        return KOLM_ECHECKSUM;
-                    }
-                }
-            }
-            const u64 a = r->starts[p.sel[i0]], b = r->starts[p.sel[i1 - 1] + 1];
-            const fnd::GroupScan gs = fnd::group_scan(S, a, b, L, g + 1 == ng, hi);
-            st.bytes_scanned += gs.n;
-            find_group(c, dec - gs.carry, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which,
-                       st.emit_launches, st.ms_find);
-            S = gs.S_next;
-            carry = (u32)(b - S);  // < L: the bytes [S, b) end the scan buffer
-            if (g + 1 < ng && carry) {
-                KOLM_HIP_CHECK(hipMemcpyAsync(keep, dec + tot - carry, carry, hipMemcpyDeviceToDevice, s));
-                c->sync();  // the next group may move the scan buffer
-            }
-        }
+        if (int e = find_over_groups(r, p, lo, hi, L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
+                find_group(c, buf, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which, st.emit_launches,
+                           st.ms_find);
+            }))
+            return e;
         if (c->timing) c->timing_collect_tail(0, nullptr);
         return KOLM_OK;
     });
@@ -4068,6 +4095,304 @@ int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* 
     if (n && !offs) return KOLM_EARG;
     std::copy(r->f_offs.begin() + first, r->f_offs.begin() + first + n, offs);
     if (which) std::copy(r->f_which.begin() + first, r->f_which.begin() + first + n, which);
+    return KOLM_OK;
+}
+
+}  // extern "C"
+
+// ---- search for a prepared pattern set (findset_core.h, k_findset.hip) ----
+// The set owns its device tables (its own allocations: the context's named scratch may move with
+// the next call) and the per-pattern counters of a call.
+struct kolm_patset {
+    kolm_ctx* c = nullptr;
+    fst::Info info{};
+    fst::Set dev{};  // the tables on the device
+    u32 *d_filter = nullptr;
+    fst::Slot* d_slots = nullptr;
+    fst::Entry* d_entries = nullptr;
+    u64 *d_blob = nullptr, *d_pcnt = nullptr;
+};
+
+namespace {
+
+void patset_release(kolm_patset* ps) {
+    for (void* q : {(void*)ps->d_filter, (void*)ps->d_slots, (void*)ps->d_entries, (void*)ps->d_blob, (void*)ps->d_pcnt})
+        if (q) (void)hipFree(q);
+}
+
+// find_group for a set.  which: the pattern indices, 32 bits each; the per-pattern counters stay
+// on the device (ps->d_pcnt) until the call ends.
+void findset_group(kolm_ctx* c, const kolm_patset* ps, const u8* buf, u32 n, u32 lo, u32 shi, u64 base, u64 limit,
+                   u64& matches, std::vector<u64>& offs, std::vector<u32>& which, u32& launches, double& ms,
+                   u64* more_than = nullptr) {
+    const u32 ntiles = fnd::tiles(n);
+    if (!ntiles) return;
+    hipStream_t s = c->stream;
+    u32* cnt = c->get<u32>("fs_cnt", ntiles);
+    u64* tot = c->get<u64>("fs_tot", 1);
+    u64* tscan = c->get<u64>("fs_scan", (size_t)ntiles + 1);
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_findset_count", n);
+        launch_findset_count(buf, n, lo, shi, ps->dev, cnt, ps->d_pcnt, s);
+    }
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)ntiles);
+        launch_find_scan(cnt, ntiles, 0, tot, tscan, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
+    u64 total = 0;
+    KOLM_HIP_CHECK(hipMemcpyAsync(&total, tot, sizeof(u64), hipMemcpyDeviceToHost, s));
+    c->sync();
+    ms += ev_ms(c->ev[6], c->ev[7]);
+    matches += total;
+    const u64 want = std::min<u64>(total, limit > offs.size() ? limit - offs.size() : 0);
+    if (more_than && want > *more_than) {
+        *more_than = want;
+        return;
+    }
+    if (!want) return;
+    const u64 cap = std::min<u64>(fst::stage_records(find_stage_bytes(), ps->info.np), 0xFFFFFFFFull);
+    const u64 slots = std::min<u64>(cap, total);  // no launch holds more than either
+    uint2* drec = c->get<uint2>("fs_rec", slots);
+    const bool one = want == total && total <= cap;  // one launch: the tile scan stays on the device
+    std::vector<u64> hscan;
+    if (!one) {
+        hscan.resize((size_t)ntiles + 1);
+        KOLM_HIP_CHECK(hipMemcpyAsync(hscan.data(), tscan, sizeof(u64) * hscan.size(), hipMemcpyDeviceToHost, s));
+        c->sync();
+    }
+    std::vector<uint2> hrec;
+    u64 got = 0;
+    for (u32 t0 = 0; got < want;) {
+        u32 t1 = ntiles;
+        u64 recs = total;
+        if (!one) {
+            while (hscan[t0 + 1] == hscan[t0]) ++t0;
+            t1 = fnd::emit_cut(hscan.data(), ntiles, t0, cap, want);
+            recs = hscan[t1] - hscan[t0];
+        }
+        KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
+        {
+            TScope t(c, KOLM_KT_EMIT, "k_findset_emit", (u64)(t1 - t0) * fnd::TILE + fst::REC_BYTES * recs);
+            launch_findset_emit(buf, n, lo, shi, ps->dev, t0, t1, tscan, drec, (u32)slots, s);
+        }
+        KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
+        const u64 take = std::min<u64>(recs, want - got);
+        hrec.resize(take);
+        KOLM_HIP_CHECK(hipMemcpyAsync(hrec.data(), drec, sizeof(uint2) * take, hipMemcpyDeviceToHost, s));
+        c->sync();
+        ms += ev_ms(c->ev[6], c->ev[7]);
+        for (u64 k = 0; k < take; ++k) offs.push_back(base + hrec[k].x), which.push_back(hrec[k].y);
+        got += take;
+        t0 = t1;
+        ++launches;
+    }
+}
+
+void findset_zero_counts(kolm_ctx* c, const kolm_patset* ps) {
+    KOLM_HIP_CHECK(hipMemsetAsync(ps->d_pcnt, 0, sizeof(u64) * ps->info.np, c->stream));
+}
+
+// the counters back once, at the end of a call (counts may be NULL)
+void findset_read_counts(kolm_ctx* c, const kolm_patset* ps, u64* counts) {
+    if (!counts) return;
+    KOLM_HIP_CHECK(hipMemcpyAsync(counts, ps->d_pcnt, sizeof(u64) * ps->info.np, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+}
+
+}  // namespace
+
+extern "C" {
+
+int kolm_patset_create(kolm_ctx* c, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, kolm_patset** out) {
+    if (!out) return KOLM_EARG;
+    *out = nullptr;
+    if (!c) c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    char msg[160];
+    if (np < 1 || np > KOLM_FIND_SET_MAX_PATTERNS) {
+        snprintf(msg, sizeof msg, "kolm_patset_create: %u patterns (1..%u are allowed)", np, (u32)KOLM_FIND_SET_MAX_PATTERNS);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    if (!pats || !pat_off) return KOLM_EARG;
+    for (u32 i = 0; i < np; ++i) {
+        if (pat_off[i + 1] <= pat_off[i]) {
+            snprintf(msg, sizeof msg, "kolm_patset_create: pattern %u is empty", i);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        const u32 len = pat_off[i + 1] - pat_off[i];
+        if (len > KOLM_FIND_MAX_LEN) {
+            snprintf(msg, sizeof msg, "kolm_patset_create: pattern %u has %u bytes (at most %u)", i, len,
+                     (u32)KOLM_FIND_MAX_LEN);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+    }
+    fst::Tables T;
+    u32 dup[2] = {0, 0};
+    if (!fst::build(pats, pat_off, np, T, dup)) {
+        snprintf(msg, sizeof msg, "kolm_patset_create: patterns %u and %u are equal (a set holds distinct patterns)", dup[0],
+                 dup[1]);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    std::unique_ptr<kolm_patset> ps(new kolm_patset);
+    ps->c = c;
+    ps->info = T.info;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->active = c->stream;  // c->sync() below waits for the uploads
+        auto up = [&](auto*& d, const auto& v) {
+            KOLM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), v.size() * sizeof(v[0])));
+            KOLM_HIP_CHECK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream));
+        };
+        up(ps->d_filter, T.filter), up(ps->d_slots, T.slots), up(ps->d_entries, T.entries), up(ps->d_blob, T.blob);
+        KOLM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ps->d_pcnt), sizeof(u64) * np));
+        c->sync();  // the host tables go out of scope
+        ps->dev = T.view();
+        ps->dev.filter = ps->d_filter, ps->dev.slots = ps->d_slots, ps->dev.entries = ps->d_entries, ps->dev.blob = ps->d_blob;
+        return KOLM_OK;
+    });
+    if (rc) {
+        patset_release(ps.get());
+        return rc;
+    }
+    *out = ps.release();
+    return KOLM_OK;
+}
+
+void kolm_patset_free(kolm_patset* ps) {
+    if (!ps) return;
+    if (ps->c) {
+        std::lock_guard<std::mutex> g(ps->c->mu);
+        (void)hipSetDevice(ps->c->device);
+        patset_release(ps);
+    }
+    delete ps;
+}
+
+int kolm_patset_info(const kolm_patset* ps, kolm_patset_info_t* out) {
+    if (!ps || !out) return KOLM_EARG;
+    *out = kolm_patset_info_t{ps->info.np,   ps->info.K, ps->info.keys,          ps->info.slots,
+                              ps->info.filter_bits, ps->info.L, ps->info.longest_bucket};
+    return KOLM_OK;
+}
+
+int kolm_find_set_device(kolm_ctx* c, const void* d_data, uint64_t n, const kolm_patset* ps, uint64_t max_results,
+                         uint64_t* counts, uint64_t* offs, uint32_t* which, uint64_t cap, uint64_t* nfound, double* ms) {
+    if (ms) *ms = 0.0;
+    if (nfound) *nfound = 0;
+    if (!c || !ps || !nfound) return KOLM_EARG;
+    if (ps->c != c) {
+        set_err("kolm_find_set_device: the pattern set belongs to another context");
+        return KOLM_EARG;
+    }
+    if (n >= (1ull << 31)) {
+        set_err("kolm_find_set_device: the buffer must be smaller than 2^31 bytes");
+        return KOLM_EARG;
+    }
+    if ((n && !d_data) || (cap && (!offs || !which))) return KOLM_EARG;
+    const u32 np = ps->info.np;
+    if (counts)
+        for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    if (n == 0) return KOLM_OK;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        c->active = c->stream;
+        findset_zero_counts(c, ps);
+        std::vector<u64> o;
+        std::vector<u32> w;
+        u32 launches = 0;
+        double t = 0.0;
+        u64 more = cap, matches = 0;
+        findset_group(c, ps, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, 0, max_results, matches, o, w, launches, t,
+                      &more);
+        findset_read_counts(c, ps, counts);
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        if (ms) *ms = t;
+        if (more > cap) {
+            *nfound = more;
+            set_err("kolm_find_set_device: result capacity too small");
+            return KOLM_ECAP;
+        }
+        *nfound = o.size();
+        std::copy(o.begin(), o.end(), offs);
+        std::copy(w.begin(), w.end(), which);
+        return KOLM_OK;
+    });
+}
+
+int kolm_reader_find_set(kolm_reader* r, const kolm_patset* ps, uint64_t lo, uint64_t hi, uint64_t max_results,
+                         uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
+    if (stats) *stats = kolm_find_stats{};
+    if (nfound) *nfound = 0;
+    if (!r || !r->c || !ps || !nfound) return KOLM_EARG;
+    // every argument check before the first launch: the set's context, the window, the selected blocks
+    if (ps->c != r->c) {
+        set_err("kolm_reader_find_set: the pattern set and the reader belong to different contexts");
+        return KOLM_EARG;
+    }
+    const u32 np = ps->info.np;
+    RangePlan p;
+    kolm_find_stats st{};
+    st.patterns = np;
+    if (int rc = find_plan("kolm_reader_find_set", r, lo, hi, p, st)) return rc;
+    if (counts)
+        for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    kolm_ctx* c = r->c;
+    std::vector<u64> offs;
+    std::vector<u32> which;
+    std::vector<u64> hc(counts ? np : 0);
+    u64 matches = 0;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
+        if (p.sel.empty()) return KOLM_OK;
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        c->active = c->stream;
+        findset_zero_counts(c, ps);
+        if (int e = find_over_groups(r, p, lo, hi, ps->info.L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
+                findset_group(c, ps, buf, gs.n, gs.lo, gs.shi, gs.start, max_results, matches, offs, which, st.emit_launches,
+                              st.ms_find);
+            }))
+            return e;
+        findset_read_counts(c, ps, counts ? hc.data() : nullptr);
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        return KOLM_OK;
+    });
+    if (rc) {  // no results leave a failed call
+        if (stats) *stats = st;
+        return rc;
+    }
+    if (counts) std::copy(hc.begin(), hc.end(), counts);
+    st.matches = matches;
+    st.returned = offs.size();
+    *nfound = offs.size();
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->fs_offs.swap(offs), r->fs_which.swap(which);
+    }
+    if (stats) *stats = st;
+    return KOLM_OK;
+}
+
+int kolm_reader_find_copy32(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint32_t* which) {
+    if (!r || !r->c) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(r->c->mu);
+    if (first > r->fs_offs.size() || n > r->fs_offs.size() - first) {
+        set_err("kolm_reader_find_copy32: more results than the last find_set holds");
+        return KOLM_EARG;
+    }
+    if (n && !offs) return KOLM_EARG;
+    std::copy(r->fs_offs.begin() + first, r->fs_offs.begin() + first + n, offs);
+    if (which) std::copy(r->fs_which.begin() + first, r->fs_which.begin() + first + n, which);
     return KOLM_OK;
 }
 

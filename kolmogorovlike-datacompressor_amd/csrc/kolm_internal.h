@@ -697,6 +697,17 @@ void launch_find_emit(const u8* buf, u32 n, u32 lo, u32 shi, const fnd::Pats* P,
                       const u64* tscan, u32* out_pos, u8* out_which, u32 cap, hipStream_t s);
 }  // namespace kolm
 
+// ---- k_findset.hip: search of a resident buffer for a prepared pattern set (findset_core.h) ----
+#include "findset_core.h"
+namespace kolm {
+// buf, n, lo, shi as above; S: the set's tables on the device.  cnt [tiles(n)]: the tiles' totals
+// (scanned by launch_find_scan with np = 0); pcnt [S.np]: every match adds 1 to its pattern's counter.
+void launch_findset_count(const u8* buf, u32 n, u32 lo, u32 shi, const fst::Set& S, u32* cnt, u64* pcnt, hipStream_t s);
+// the records (position, pattern index) of tiles [t0, t1) to out [cap], the first at slot 0
+void launch_findset_emit(const u8* buf, u32 n, u32 lo, u32 shi, const fst::Set& S, u32 t0, u32 t1, const u64* tscan,
+                         uint2* out, u32 cap, hipStream_t s);
+}  // namespace kolm
+
 #define KOLM_HIP_CHECK(x)                                              \
     do {                                                               \
         hipError_t e_ = (x);                                           \

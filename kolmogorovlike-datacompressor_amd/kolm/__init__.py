@@ -51,7 +51,7 @@ __all__ = [
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
-    "open_container", "Reader", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
+    "open_container", "Reader", "PatternSet", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
     "Checksums", "KolmChecksumError", "crc32_blocks", "crc32_combine", "last_checksums", "checksums_of", "check",
 ]
 
@@ -569,6 +569,7 @@ class Reader:
     def __init__(self, container: bytes, ctx=None, checksums=None):
         blob = bytes(container)
         self._cs = None if checksums is None else as_checksums(checksums)
+        self._ctx = ctx
         self._h, info = _lib.reader_open(blob, ctx)
         self.mode, self.size_field = info["mode"], info["size_field"]
         self._total = info["total_len"]
@@ -750,6 +751,60 @@ class Reader:
         """The number of matches of every pattern."""
         return self._search(patterns, start, end, 0)[2]
 
+    def _search_set(self, pset, start, end, limit):
+        """(offsets, pattern indices, counts) of a PatternSet (or a sequence of patterns: a
+        temporary set, closed before returning) in data[start:end]."""
+        global _last_find
+        h = self._handle()
+        if not isinstance(pset, PatternSet):
+            with PatternSet(pset, self._ctx) as tmp:
+                return self._search_set(tmp, start, end, limit)
+        ph = pset._handle()
+        pats = pset.patterns
+        start, end = int(start), self._total if end is None else int(end)
+        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
+            raise ValueError("start, end and limit must not be negative")
+        lo, hi = min(start, self._total), min(end, self._total)
+        if lo >= hi:  # nothing to search: no device call
+            return [], [], [0] * len(pats)
+        if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
+            data = self._read_host([(lo, hi - lo)])[0]
+            by_len: Dict[int, Dict[bytes, int]] = {}
+            for i, p in enumerate(pats):
+                by_len.setdefault(len(p), {})[p] = i
+            hits, counts = [], [0] * len(pats)
+            for ln, table in by_len.items():
+                for o in range(len(data) - ln + 1):
+                    i = table.get(data[o:o + ln])
+                    if i is not None:
+                        hits.append((lo + o, i))
+                        counts[i] += 1
+            hits.sort()
+            if limit is not None:
+                hits = hits[:int(limit)]
+            rd = dict(_last_read)
+            _last_find = {"host": True, "patterns": len(pats), "matches": sum(counts), "returned": len(hits),
+                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
+                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
+                          "ms_find": 0.0}
+            return [o for o, _ in hits], [i for _, i in hits], counts
+        offs, which, counts = _lib.reader_find_set(h, ph, len(pats), lo, hi, limit)
+        _last_find = {}
+        return offs, which, counts
+
+    def find_set(self, pset, start: int = 0, end: Optional[int] = None,
+                 limit: Optional[int] = None) -> List[Tuple[int, int]]:
+        """(offset, pattern index) of every match of a PatternSet (up to 65 536 distinct
+        patterns) in data[start:end], sorted: the shape of find_many, from one decode of the
+        window and one pass over it (kolm_reader_find_set).  start / end / limit as find.  A
+        plain sequence of patterns is accepted too: a temporary set."""
+        offs, which, _ = self._search_set(pset, start, end, limit)
+        return list(zip(offs, which))
+
+    def count_set(self, pset, start: int = 0, end: Optional[int] = None) -> List[int]:
+        """The number of matches of every pattern of the set (no emit launch)."""
+        return self._search_set(pset, start, end, 0)[2]
+
     def read_many_device(self, ranges, dptr: int, cap: int) -> List[int]:
         """The ranges' bytes packed back to back at the device address dptr (cap bytes
         available), left on the device; returns every range's offset in that buffer.  Ranges
@@ -769,9 +824,51 @@ class Reader:
             pos += n
         return offs
 
+class PatternSet:
+    """Up to 65 536 pairwise distinct patterns of 1..256 bytes, prepared once for
+    Reader.find_set / count_set (kolm_patset_create): the hashed tables of the set live on the
+    device until close().  ctx (optional): a context of kolm._lib.device_ctx instead of the
+    default one; a set serves the readers of its own context.  ValueError for no pattern, more
+    than 65 536, an empty one, one of more than 256 bytes and two equal ones.  `.patterns` is
+    the tuple of the patterns, `.info` the set's kolm_patset_info: np, key_bytes, keys, slots,
+    filter_bits, longest, longest_bucket."""
+
+    def __init__(self, patterns, ctx=None):
+        self._h = None
+        self.patterns: Tuple[bytes, ...] = tuple(_lib.set_patterns(patterns))
+        self._h, self.info = _lib.patset_create(self.patterns, ctx)
+
+    def __len__(self) -> int:
+        return len(self.patterns)
+
+    def __enter__(self) -> "PatternSet":
+        return self
+
+    def __exit__(self, *exc) -> bool:
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if not sys.is_finalizing():
+                self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            _lib.patset_free(h)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("operation on closed pattern set")
+        return self._h
+
 
 def last_find() -> Dict[str, Any]:
-    """kolm_find_stats of the last Reader.find / find_many / count / count_many: patterns,
+    """kolm_find_stats of the last Reader.find / find_many / count / count_many / find_set /
+    count_set: patterns,
     matches (total, whatever the limit), returned, blocks_decoded, groups, emit_launches,
     bytes_decoded, bytes_scanned, ms_decode, ms_find (a call served on the host reports its
     blocks and matches with groups = 0 and "host": True)."""

@@ -176,6 +176,21 @@ class FindStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PatsetInfo(ctypes.Structure):
+    _fields_ = [
+        ("np", ctypes.c_uint32),
+        ("key_bytes", ctypes.c_uint32),
+        ("keys", ctypes.c_uint32),
+        ("slots", ctypes.c_uint32),
+        ("filter_bits", ctypes.c_uint32),
+        ("longest", ctypes.c_uint32),
+        ("longest_bucket", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RangeSeg(ctypes.Structure):
     _fields_ = [("src", ctypes.c_uint64), ("dst", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
@@ -281,9 +296,17 @@ SIGNATURES = [
                                ctypes.POINTER(ctypes.c_double)]),
     ("kolm_reader_find", I32, [P, P, P, U32, U64, U64, U64, P, ctypes.POINTER(U64), ctypes.POINTER(FindStats)]),
     ("kolm_reader_find_copy", I32, [P, U64, U64, P, P]),
+    ("kolm_patset_create", I32, [P, P, P, U32, ctypes.POINTER(P)]),
+    ("kolm_patset_free", None, [P]),
+    ("kolm_patset_info", I32, [P, ctypes.POINTER(PatsetInfo)]),
+    ("kolm_find_set_device", I32, [P, P, U64, P, U64, P, P, P, U64, ctypes.POINTER(U64),
+                                   ctypes.POINTER(ctypes.c_double)]),
+    ("kolm_reader_find_set", I32, [P, P, U64, U64, U64, P, ctypes.POINTER(U64), ctypes.POINTER(FindStats)]),
+    ("kolm_reader_find_copy32", I32, [P, U64, U64, P, P]),
 ]
 KOLM_FIND_MAX_PATTERNS = 16
 KOLM_FIND_MAX_LEN = 256
+KOLM_FIND_SET_MAX_PATTERNS = 65536
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
 KOLM_ERCCL = -4
@@ -1297,6 +1320,105 @@ def reader_find(h, patterns, lo: int, hi: int, limit=None):
     check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
     _last_find = st.as_dict()
     return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]]
+
+
+# ---- pattern sets (kolm_patset_create, kolm_find_set_device, kolm_reader_find_set) ---------
+
+def set_patterns(patterns) -> list:
+    """The patterns of a set as a list of bytes; ValueError for what the library refuses (no
+    pattern or more than 65 536, an empty one, one of more than 256 bytes, two equal ones)."""
+    if isinstance(patterns, (bytes, bytearray, memoryview, str)):
+        raise TypeError("patterns must be a sequence of bytes-like objects")
+    pats = [memoryview(p).tobytes() for p in patterns]
+    if not 1 <= len(pats) <= KOLM_FIND_SET_MAX_PATTERNS:
+        raise ValueError(f"{len(pats)} patterns (1..{KOLM_FIND_SET_MAX_PATTERNS} are allowed)")
+    seen = {}
+    for i, p in enumerate(pats):
+        if not p:
+            raise ValueError(f"pattern {i} is empty")
+        if len(p) > KOLM_FIND_MAX_LEN:
+            raise ValueError(f"pattern {i} has {len(p)} bytes (at most {KOLM_FIND_MAX_LEN})")
+        if seen.setdefault(p, i) != i:
+            raise ValueError(f"patterns {seen[p]} and {i} are equal (a set holds distinct patterns)")
+    return pats
+
+
+def patset_create(patterns, ctx=None):
+    """kolm_patset_create on ctx (None: the default context) with the patterns as given: the
+    library's argument errors raise ValueError.  Returns (handle, info dict)."""
+    ensure_init()
+    pats = list(patterns)
+    flat, off = _pattern_arrays(pats)
+    h = ctypes.c_void_p()
+    L = load()
+    rc = L.kolm_patset_create(ctx, flat.ctypes.data, off.ctypes.data, len(pats), ctypes.byref(h))
+    if rc == -1:
+        raise ValueError(L.kolm_last_error().decode())
+    check(rc)
+    info = PatsetInfo()
+    check(L.kolm_patset_info(h, ctypes.byref(info)))
+    return h, info.as_dict()
+
+
+def patset_free(h):
+    load().kolm_patset_free(h)
+
+
+def find_set_device(ctx, dptr: int, n: int, pset, limit=None, cap=None):
+    """kolm_find_set_device over the n bytes at the device address dptr with the set handle
+    pset (np from its info).  Returns (offsets, pattern indices, counts per pattern, device ms).
+    cap: the capacity of the first call (default 0: the two-call pattern always runs)."""
+    L = load()
+    info = PatsetInfo()
+    check(L.kolm_patset_info(pset, ctypes.byref(info)))
+    counts = np.zeros(info.np, dtype=np.uint64)
+    nfound, ms = U64(0), ctypes.c_double(0.0)
+    lim = NO_LIMIT if limit is None else int(limit)
+    k = int(cap or 0)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint32)
+    rc = L.kolm_find_set_device(ctx, dptr, n, pset, lim, counts.ctypes.data, offs.ctypes.data, which.ctypes.data, k,
+                                ctypes.byref(nfound), ctypes.byref(ms))
+    if rc == -1:
+        raise ValueError(L.kolm_last_error().decode())
+    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
+        k = int(nfound.value)
+        offs = np.zeros(max(k, 1), dtype=np.uint64)
+        which = np.zeros(max(k, 1), dtype=np.uint32)
+        rc = L.kolm_find_set_device(ctx, dptr, n, pset, lim, counts.ctypes.data, offs.ctypes.data, which.ctypes.data, k,
+                                    ctypes.byref(nfound), ctypes.byref(ms))
+    check(rc)
+    k = int(nfound.value)
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts], ms.value
+
+
+def find_set_bytes(data, patterns, limit=None, data_offset: int = 0, device: int = None, cap=None):
+    """Uploads data data_offset (0..15) bytes into a buffer, makes a set of the patterns in that
+    buffer's context and searches (find_set_device)."""
+    def run(ctx, p):
+        h, _ = patset_create(patterns, ctx)
+        try:
+            return find_set_device(ctx, p, len(data), h, limit, cap)
+        finally:
+            patset_free(h)
+    return _on_device(data, data_offset, device, run)
+
+
+def reader_find_set(h, pset, np_: int, lo: int, hi: int, limit=None):
+    """kolm_reader_find_set + kolm_reader_find_copy32.  Returns (offsets, pattern indices, counts
+    per pattern); the stats go to last_find().  Errors as reader_find."""
+    global _last_find
+    counts = np.zeros(max(np_, 1), dtype=np.uint64)
+    nfound = U64(0)
+    st = FindStats()
+    lim = NO_LIMIT if limit is None else int(limit)
+    _read_check(load().kolm_reader_find_set(h, pset, lo, hi, lim, counts.ctypes.data, ctypes.byref(nfound), ctypes.byref(st)))
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint32)
+    check(load().kolm_reader_find_copy32(h, 0, k, offs.ctypes.data, which.ctypes.data))
+    _last_find = st.as_dict()
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:np_]]
 
 
 def reader_read_device(h, ranges, dptr: int, cap: int):

@@ -1,0 +1,338 @@
+// CPU emulation of the pattern-set search kernels: the header k_findset_count / k_findset_emit of
+// kolmogorovlike-datacompressor_amd/csrc/k_findset.hip compile (csrc/findset_core.h, on top of
+// csrc/find_core.h), driven with the kernels' shape -- a workgroup per span of 4 KiB tiles, 256
+// virtual threads with 16 positions each, filter bit / probe / bucket walk per position, the
+// per-tile totals and per-pattern counters, the exclusive scan of the tile totals, the emit
+// launches cut at scanned tile boundaries so that each fits the staging array -- behind a C
+// interface for tests/test_findset_core.py, and a main() that runs the sweeps on its own.  The data
+// goes through find_emu.cpp's recording loader (every load checked against the load contract, on
+// heap buffers of exactly the aligned words it allows); the set's tables are heap vectors of
+// exact size, so under -fsanitize=address,undefined a probe, a bucket walk or a tail compare that
+// leaves them is an error.
+//   g++ -O2 -std=c++17 -shared -fPIC tools/findset_emu.cpp -o findset_emu.so
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined tools/findset_emu.cpp -o findset_emu
+//   ./findset_emu     exit status 0 when every case matches the byte-by-byte reference
+#define FND_EMU_NO_MAIN 1
+#include "find_emu.cpp"  // Ld (the recording loader), noise, g_cases
+
+#include "../kolmogorovlike-datacompressor_amd/csrc/findset_core.h"
+
+namespace {
+
+struct SetEmu {
+    fst::Tables T;
+    fst::Set S;
+};
+
+struct FsEmu {
+    Ld ld;
+    u32 lo, shi;
+    const fst::Set& S;
+    u32 mis() const { return (u32)(reinterpret_cast<uintptr_t>(ld.buf) & (WORD - 1)); }
+
+    // one thread of one tile: f(position, entry) for its matches, positions ascending
+    template <class F>
+    u32 run_thread(u32 tile, u32 t, F&& f) {
+        const u32 p0 = tile * TILE + t * PER;
+        u64 w[PER];
+        windows(ld, mis(), p0, ld.n, w);
+        u32 c = 0;
+        for (u32 j = 0; j < PER; ++j)
+            c += fst::for_matches(S, S.filter, ld, w[j], mis(), p0 + j, lo, shi, ld.n,
+                                  [&](const fst::Entry& e) { f(p0 + j, e); });
+        return c;
+    }
+    // k_findset_count: the workgroups walk their spans
+    void count(u32 ntiles, std::vector<u32>& cnt, u64* pcnt) {
+        cnt.assign(ntiles, 0);
+        const u32 span = fst::span_tiles(S.filter_words * 4);
+        for (u32 wg = 0; wg < fst::spans(ntiles, span); ++wg)
+            for (u32 tile = wg * span; tile < std::min(ntiles, (wg + 1) * span); ++tile)
+                for (u32 t = 0; t < WG; ++t) cnt[tile] += run_thread(tile, t, [&](u32, const fst::Entry& e) { ++pcnt[e.idx]; });
+    }
+    // k_findset_emit over tiles [t0, t1)
+    u64 emit(u32 t0, u32 t1, const u64* tscan, u32* pos, u32* which, u64 cap) {
+        u64 over = 0;
+        const u32 span = fst::span_tiles(S.filter_words * 4);
+        for (u32 wg = 0; wg < fst::spans(t1 - t0, span); ++wg)
+            for (u32 tile = t0 + wg * span; tile < std::min(t1, t0 + (wg + 1) * span); ++tile) {
+                u64 slot = tscan[tile] - tscan[t0];
+                for (u32 t = 0; t < WG; ++t)
+                    run_thread(tile, t, [&](u32 o, const fst::Entry& e) {
+                        if (slot < cap) pos[slot] = o, which[slot] = e.idx;
+                        else ++over;
+                        ++slot;
+                    });
+                if (slot != tscan[tile + 1] - tscan[t0]) ++over;  // the count and the emit disagree
+            }
+        return over;
+    }
+};
+
+// One group as the host runs it (findset_group of kolm_api.cpp).
+u64 fs_group(const u8* buf, u32 n, u32 lo, u32 shi, const fst::Set& S, u64 base, u64 stage_bytes, u64 limit, u64* pcnt,
+             std::vector<u64>& offs, std::vector<u32>& which, u32* launches) {
+    FsEmu e{Ld{buf, n}, lo, shi, S};
+    const u32 ntiles = tiles(n);
+    if (!ntiles) return 0;
+    std::vector<u32> cnt;
+    e.count(ntiles, cnt, pcnt);
+    std::vector<u64> tscan((size_t)ntiles + 1, 0);
+    for (u32 t = 0; t < ntiles; ++t) tscan[t + 1] = tscan[t] + cnt[t];
+    const u64 room = limit > offs.size() ? limit - offs.size() : 0;
+    const u64 want = std::min<u64>(tscan[ntiles], room);
+    const u64 cap = fst::stage_records(stage_bytes, S.np);
+    std::vector<u32> spos(std::min<u64>(cap, tscan[ntiles])), swhich(spos.size());  // exact: ASan sees a slot past them
+    u64 got = 0, bad = 0;
+    for (u32 t0 = 0; got < want;) {
+        while (tscan[t0 + 1] == tscan[t0]) ++t0;
+        const u32 t1 = emit_cut(tscan.data(), ntiles, t0, cap, want);
+        bad += e.emit(t0, t1, tscan.data(), spos.data(), swhich.data(), spos.size());
+        const u64 take = std::min<u64>(tscan[t1] - tscan[t0], want - got);
+        for (u64 k = 0; k < take; ++k) offs.push_back(base + spos[k]), which.push_back(swhich[k]);
+        got += take;
+        t0 = t1;
+        ++*launches;
+    }
+    return bad + e.ld.bad;
+}
+
+bool set_args_ok(const u32* pat_off, u32 np) {
+    if (np < 1 || np > fst::MAX_PATTERNS) return false;
+    for (u32 i = 0; i < np; ++i)
+        if (pat_off[i + 1] <= pat_off[i] || pat_off[i + 1] - pat_off[i] > MAX_LEN) return false;
+    return true;
+}
+
+void hand_out(const std::vector<u64>& o, const std::vector<u32>& w, u64* offs, u32* which, u64 cap, u64* nfound) {
+    *nfound = o.size();
+    for (u64 k = 0; k < o.size() && k < cap; ++k) offs[k] = o[k], which[k] = w[k];
+}
+
+}  // namespace
+
+// fst::build.  info [7]: np, K, keys, slots, filter bits, L, longest bucket.  NULL for bad
+// arguments (dup = {~0, ~0}) and for two equal patterns (dup = their indices).
+extern "C" void* fst_emu_build(const uint8_t* pats, const uint32_t* pat_off, uint32_t np, uint32_t* info, uint32_t* dup) {
+    dup[0] = dup[1] = ~0u;
+    if (!set_args_ok(pat_off, np)) return nullptr;
+    SetEmu* h = new SetEmu;
+    if (!fst::build(pats, pat_off, np, h->T, dup)) {
+        delete h;
+        return nullptr;
+    }
+    h->S = h->T.view();
+    const fst::Info& I = h->T.info;
+    const u32 v[7] = {I.np, I.K, I.keys, I.slots, I.filter_bits, I.L, I.longest_bucket};
+    std::copy(v, v + 7, info);
+    return h;
+}
+
+extern "C" void fst_emu_free(void* h) { delete static_cast<SetEmu*>(h); }
+
+// Table facts for the build test: occupied slots, set filter bits, and the number of patterns
+// (given again) that fst::bucket_of does not lead to -- a bucket that holds the pattern's index,
+// in ascending index order, with the pattern's bytes in the blob.
+extern "C" uint32_t fst_emu_check_tables(const void* hv, const uint8_t* pats, const uint32_t* pat_off, uint32_t* occupied,
+                                         uint32_t* filter_set) {
+    const SetEmu* h = static_cast<const SetEmu*>(hv);
+    *occupied = *filter_set = 0;
+    for (const fst::Slot& s : h->T.slots) *occupied += s.count != 0;
+    for (u32 v : h->T.filter) *filter_set += (u32)__builtin_popcount(v);
+    u32 missing = 0;
+    for (u32 i = 0; i < h->T.info.np; ++i) {
+        const u32 len = pat_off[i + 1] - pat_off[i];
+        u64 key = 0;
+        for (u32 k = 0; k < len && k < h->T.info.K; ++k) key |= (u64)pats[pat_off[i] + k] << (8 * k);
+        u32 first = 0;
+        const u32 cnt = fst::bucket_of(h->S, h->S.filter, key, first);
+        bool found = false, ordered = true;
+        for (u32 k = 0; k < cnt; ++k) {
+            const fst::Entry& e = h->T.entries[first + k];
+            if (k && h->T.entries[first + k - 1].idx >= e.idx) ordered = false;
+            if (e.idx != i || e.len != len) continue;
+            found = true;
+            for (u32 b = 0; b < (len + 7) / 8 * 8; ++b)
+                if ((u8)(h->T.blob[e.word + (b >> 3)] >> (8 * (b & 7))) != (b < len ? pats[pat_off[i] + b] : 0)) found = false;
+        }
+        missing += !(found && ordered);
+    }
+    return missing;
+}
+
+// The search of buf [0, n) (any alignment; the aligned words around it must be readable) for
+// matches that start in [lo, n).  counts [np] exact; the first min(total, limit) matches to
+// offs / which (cap entries); nfound their number; launches = emit launches.  Returns the number
+// of contract violations.
+extern "C" uint64_t fst_emu_find(const void* hv, const uint8_t* buf, uint32_t n, uint32_t lo, uint64_t stage_bytes,
+                                 uint64_t limit, uint64_t* counts, uint64_t* offs, uint32_t* which, uint64_t cap,
+                                 uint64_t* nfound, uint32_t* launches) {
+    const SetEmu* h = static_cast<const SetEmu*>(hv);
+    std::vector<u64> o;
+    std::vector<u32> w;
+    u32 l = 0;
+    std::fill(counts, counts + h->S.np, 0);
+    const u64 bad = fs_group(buf, n, lo, n, h->S, 0, stage_bytes, limit, counts, o, w, &l);
+    *launches = l;
+    hand_out(o, w, offs, which, cap, nfound);
+    return bad;
+}
+
+// The grouped search as the reader runs it: data is the whole stream, group g its bytes
+// [bounds[g], bounds[g + 1]).  Every group's scan buffer is a heap block of exactly the aligned
+// words around [carry][the group's bytes], the carry ending at a 256-byte boundary as on the device.
+extern "C" uint64_t fst_emu_find_grouped(const void* hv, const uint8_t* data, const uint64_t* bounds, uint32_t ng, uint64_t lo,
+                                         uint64_t hi, uint64_t stage_bytes, uint64_t limit, uint64_t* counts, uint64_t* offs,
+                                         uint32_t* which, uint64_t cap, uint64_t* nfound, uint32_t* launches) {
+    const SetEmu* h = static_cast<const SetEmu*>(hv);
+    const u32 L = h->T.info.L;
+    std::vector<u64> o;
+    std::vector<u32> w;
+    u32 l = 0;
+    u64 bad = 0, S = lo;
+    std::fill(counts, counts + h->S.np, 0);
+    for (u32 g = 0; g < ng; ++g) {
+        const GroupScan gs = group_scan(S, bounds[g], bounds[g + 1], L, g + 1 == ng, hi);
+        const u32 front = (MAX_LEN - gs.carry) & (WORD - 1);  // misalignment of the scan buffer
+        const u64 size = ((u64)front + gs.n + WORD - 1) / WORD * WORD;
+        u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
+        std::memset(raw, 0xEE, size);
+        std::memcpy(raw + front, data + gs.start, gs.n);
+        bad += fs_group(raw + front, gs.n, gs.lo, gs.shi, h->S, gs.start, stage_bytes, limit, counts, o, w, &l);
+        std::free(raw);
+        S = gs.S_next;
+    }
+    *launches = l;
+    hand_out(o, w, offs, which, cap, nfound);
+    return bad;
+}
+
+extern "C" uint32_t fst_emu_span_tiles(uint32_t filter_bytes) { return fst::span_tiles(filter_bytes); }
+
+namespace {
+
+typedef std::vector<std::vector<u8>> PatList;
+typedef std::vector<std::pair<u64, u32>> SetHits;
+
+SetHits set_reference(const std::vector<u8>& d, const PatList& pats) {
+    SetHits h;
+    for (size_t i = 0; i < pats.size(); ++i)
+        for (u64 o = 0; o + pats[i].size() <= d.size(); ++o)
+            if (std::memcmp(d.data() + o, pats[i].data(), pats[i].size()) == 0) h.push_back({o, (u32)i});
+    std::sort(h.begin(), h.end());
+    return h;
+}
+
+// data at misalignment m in a heap block of exactly the aligned words around it; `want` (optional)
+// replaces the byte-by-byte reference where that would take too long
+int run_set_case(const std::vector<u8>& d, u32 m, const PatList& pats, u64 stage, const char* what, u32 min_launches = 0,
+                 const SetHits* want_in = nullptr) {
+    const u32 n = (u32)d.size();
+    const u64 size = ((u64)m + n + WORD - 1) / WORD * WORD;
+    u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
+    std::memset(raw, 0xEE, size);
+    if (n) std::memcpy(raw + m, d.data(), n);
+    std::vector<u8> flat;
+    std::vector<u32> off{0};
+    for (auto& p : pats) flat.insert(flat.end(), p.begin(), p.end()), off.push_back((u32)flat.size());
+    flat.push_back(0);
+    u32 info[7], dup[2];
+    void* h = fst_emu_build(flat.data(), off.data(), (u32)pats.size(), info, dup);
+    int fail = h == nullptr;
+    if (h) {
+        const SetHits want = want_in ? *want_in : set_reference(d, pats);
+        std::vector<u64> counts(pats.size()), offs(want.size() + 1), expect(pats.size());
+        std::vector<u32> which(want.size() + 1);
+        u64 nfound = 0;
+        u32 launches = 0;
+        const u64 bad = fst_emu_find(h, raw + m, n, 0, stage, ~0ull, counts.data(), offs.data(), which.data(), offs.size(),
+                                     &nfound, &launches);
+        fail = bad != 0 || nfound != want.size() || launches < min_launches;
+        for (size_t k = 0; k < want.size() && !fail; ++k) fail = offs[k] != want[k].first || which[k] != want[k].second;
+        for (auto& x : want) ++expect[x.second];
+        fail |= counts != expect;
+        if (fail)
+            std::fprintf(stderr, "%s: n %u, misalignment %u, %zu patterns, K %u: %llu violations, %llu found, %zu expected, %u launches\n",
+                         what, n, m, pats.size(), info[1], (unsigned long long)bad, (unsigned long long)nfound, want.size(),
+                         launches);
+        fst_emu_free(h);
+    } else {
+        std::fprintf(stderr, "%s: the set was refused (%u, %u)\n", what, dup[0], dup[1]);
+    }
+    std::free(raw);
+    ++g_cases;
+    return fail;
+}
+
+}  // namespace
+
+int main() {
+    int bad = 0;
+    const u32 ns[] = {0, 1, 15, 16, 17, 4095, 4096, 4097, 8193};
+    const u32 lens[] = {1, 2, 3, 7, 8, 9, 15, 16, 17, 255, 256};
+    const u32 nlens = sizeof lens / sizeof lens[0];
+    for (u32 m = 0; m < 16; ++m)
+        for (u32 n : ns)
+            for (u32 a = 0; a < nlens; ++a) {
+                // a set of lengths lens[a..]: K = min(8, lens[a]); patterns drawn from two-letter noise,
+                // one of each length planted at the start, across the tile boundary and at the very
+                // end, and its truncation (a different last byte) beside it
+                std::vector<u8> d = noise(n, 31 * m + a, 2);
+                PatList pats;
+                for (u32 b = a; b < nlens; b += 2) {
+                    std::vector<u8> p = noise(lens[b], 500 + lens[b] + m, 2);
+                    auto plant = [&](u64 o) {
+                        if (o + p.size() <= n) std::memcpy(d.data() + o, p.data(), p.size());
+                    };
+                    plant(b * 300), plant(TILE - (lens[b] + 1) / 2), plant(2 * (u64)TILE - 1);
+                    if (n >= p.size()) plant(n - p.size());
+                    pats.push_back(p);
+                    if (p.size() < MAX_LEN) {
+                        p.push_back((u8)(p.back() ^ 0x55));
+                        pats.push_back(p);
+                    }
+                }
+                bad |= run_set_case(d, m, pats, STAGE_DEFAULT, "mixed lengths");
+                // zeros, and a zero pattern one byte longer than the data's zero tail
+                std::vector<u8> z(n, 0);
+                if (n > 3) z[n / 2] = 1;
+                const u32 tail = n > 3 ? n - n / 2 - 1 : n;
+                PatList zp{std::vector<u8>(lens[a], 0)};
+                if (tail + 1 <= MAX_LEN && tail + 1 != lens[a]) zp.push_back(std::vector<u8>(tail + 1, 0));
+                bad |= run_set_case(z, m, zp, STAGE_DEFAULT, "zeros");
+            }
+    // the prefix chain: 256 matches per position, the staging minimum, several emit launches
+    {
+        PatList chain;
+        for (u32 k = 1; k <= 256; ++k) chain.push_back(std::vector<u8>(k, 0));
+        for (u32 m : {0u, 9u}) bad |= run_set_case(std::vector<u8>(2 * TILE + 300, 0), m, chain, 1, "prefix chain", 3);
+    }
+    // K = 1 with long buckets: one 1-byte pattern among 300 longer ones
+    {
+        std::vector<u8> d = noise(3 * TILE + 11, 5, 3);
+        PatList pats{std::vector<u8>(1, 'b')};
+        for (u32 k = 0; k < 300; ++k) pats.push_back(std::vector<u8>(d.begin() + 7 * k, d.begin() + 7 * k + 2 + k % 9));
+        std::sort(pats.begin(), pats.end());
+        pats.erase(std::unique(pats.begin(), pats.end()), pats.end());
+        bad |= run_set_case(d, 3, pats, STAGE_DEFAULT, "K = 1");
+    }
+    // 4 096 patterns of 6 bytes over four-letter noise: probe chains and filter collisions
+    {
+        std::vector<u8> d = noise(5 * TILE + 1, 9, 4);
+        PatList pats;
+        for (u32 k = 0; k < 4096; ++k) {
+            std::vector<u8> p(6);
+            for (u32 b = 0; b < 6; ++b) p[b] = (u8)('a' + ((k >> (2 * b)) & 3));
+            pats.push_back(p);
+        }
+        SetHits want;  // every 6-gram of the noise is in the set: pattern index = its base-4 value
+        for (u64 o = 0; o + 6 <= d.size(); ++o) {
+            u32 k = 0;
+            for (u32 b = 0; b < 6; ++b) k |= (u32)(d[o + b] - 'a') << (2 * b);
+            want.push_back({o, k});
+        }
+        bad |= run_set_case(d, 7, pats, STAGE_DEFAULT, "4096 patterns", 0, &want);
+    }
+    std::printf("findset_emu: %llu cases %s\n", (unsigned long long)g_cases, bad ? "FAILED" : "ok");
+    return bad;
+}
