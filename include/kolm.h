@@ -60,6 +60,8 @@ extern "C" {
                               decode to its input (message names block, method, offset) */
 #define KOLM_ECHECKSUM (-9) /* decoded bytes do not match the expected CRC-32 (message: block,
                               method, expected, got) */
+#define KOLM_ELINES (-10)   /* the attached line index does not describe the decoded bytes (message:
+                              block, expected count, actual count) */
 
 /* Candidate method ids (index into PY _select_encoders(), PY:2152-2165). */
 #define KOLM_M_RAW 0
@@ -671,6 +673,83 @@ int kolm_check_container(const uint8_t* container, uint64_t cn, const uint32_t* 
  * before anything is gathered (one more round trip per group): a mismatch makes the call return
  * KOLM_ECHECKSUM, and nothing is written to the output. */
 int kolm_reader_set_checksums(kolm_reader* r, const uint32_t* crc, uint32_t nblocks);
+
+/* ---- line index: count, locate and read a container's lines (lines_core.h, k_lines.hip) --- */
+/* delim is one byte value.  D = the bytes of the decoded stream equal to delim, pos(k) the offset
+ * of the k-th (0 <= k < D).  The stream's lines are what splitting at every delimiter gives: D + 1
+ * lines, line k = [start_k, end_k) with start_0 = 0, start_k = pos(k - 1) + 1, end_k = pos(k) for
+ * k < D and end_D = total_len; delimiters belong to no line, empty lines exist, an empty stream
+ * has one empty line.  line_of(o), 0 <= o <= total_len, = the delimiters in [0, o).
+ * The line index is one u32 per block: the block's delimiter count.  The container does not carry
+ * it and does not change (kolm.lines: a sidecar).  With it every line question is block-local:
+ * delimiter k lies in the one block a search of the counts' prefix sums names. */
+/* Delimiter counts of the blocks of d_data (device; bounds as kolm_crc32_blocks_device: h_bounds[0]
+ * = 0, non-decreasing, nblocks + 1 host entries, total < 2^31; any alignment): counts[i].  One
+ * streaming read (k_delim_count).  *ms (optional): its device time. */
+int kolm_delim_count_device(kolm_ctx* ctx, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks, uint32_t delim,
+                            uint32_t* counts, double* ms);
+/* The same, and the counts of the blocks' 4 KiB pieces (block i's ceil(len / 4096) pieces behind
+ * those of the blocks before it): piece_counts[0, cap) (KOLM_ECAP when cap < their number).  This
+ * is the pass the line queries run on a decoded group; *ms covers k_delim_count and the scan of the
+ * piece counts behind it. */
+int kolm_delim_count_pieces_device(kolm_ctx* ctx, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks,
+                                   uint32_t delim, uint32_t* counts, uint32_t* piece_counts, uint64_t cap, double* ms);
+/* Host only, usable without a GPU.  Delimiter numbers idx[0, n) -> the block that holds each and its
+ * number inside that block (never a block without delimiters).  KOLM_EARG, the message naming the
+ * entry, for a number at or above D = the sum of counts. */
+int kolm_lines_locate(const uint32_t* counts, uint32_t nblocks, const uint64_t* idx, uint32_t n, uint32_t* block,
+                      uint32_t* j);
+/* Host only.  Stream offsets offs[0, n) -> the block that holds the byte (never an empty one; nblocks
+ * for offs = total_len), the offset inside it and the delimiters in front of the block.  KOLM_EARG,
+ * the message naming the entry, for an offset above total_len = the sum of orig_lens. */
+int kolm_lines_locate_offsets(const uint32_t* orig_lens, const uint32_t* counts, uint32_t nblocks, const uint64_t* offs,
+                              uint32_t n, uint32_t* block, uint32_t* in_block, uint64_t* before);
+typedef struct kolm_lines_stats {
+    uint32_t queries;         /* rank / select queries answered on the device */
+    uint32_t blocks_decoded;
+    uint32_t groups;          /* decode groups (bounded scratch: KOLM_READ_BYTES) */
+    uint32_t reserved;
+    uint64_t bytes_decoded;
+    double ms_decode;         /* device time of the decode kernels (HIP events) */
+    double ms_lines;          /* device time of k_delim_count, the scan and k_delim_query */
+} kolm_lines_stats;
+/* Attaches a line index to the reader: counts[nblocks] for delim (nblocks = the reader's block
+ * count, KOLM_EARG otherwise; counts == NULL detaches). */
+int kolm_reader_set_lines(kolm_reader* r, uint32_t delim, const uint32_t* counts, uint32_t nblocks);
+/* Builds the index and attaches it: every block is decoded in the groups of kolm_range_plan
+ * (KOLM_READ_BYTES), k_delim_count runs on each group's scratch and only the counts come back:
+ * counts[0, cap) (optional; KOLM_ECAP when cap < the block count).  With checksums set each group is
+ * checked first.  KOLM_EARG for a block the device does not decode. */
+int kolm_reader_index_lines(kolm_reader* r, uint32_t delim, uint32_t* counts, uint32_t cap, kolm_lines_stats* stats);
+/* starts[i], ends[i] of lines[i], i < n.  Every delimiter needed is located once (lines k and k + 1
+ * share pos(k); line 0's start and line D's end need none), only the blocks that hold one are
+ * decoded, grouped as a read's blocks are; per group: decode, k_delim_count with piece counts, their
+ * scan, k_delim_query (one SELECT per delimiter), one copy of the results.
+ * Every argument is checked before the first launch: KOLM_EARG without an attached index, for a
+ * line above D (the message names the entry) and for a selected block the device does not decode.
+ * With checksums set each decoded group is checked before any result leaves (KOLM_ECHECKSUM).
+ * A block whose real count differs from the index, or a SELECT that finds no delimiter, gives
+ * KOLM_ELINES (the message names the block, the expected and the actual count).  A failed call
+ * writes no result.  The results do not depend on KOLM_READ_BYTES. */
+int kolm_reader_line_spans(kolm_reader* r, const uint64_t* lines, uint32_t n, uint64_t* starts, uint64_t* ends,
+                           kolm_lines_stats* stats);
+/* lines[i] = line_of(offs[i]), i < n: the same group loop with one RANK per offset.  An offset at a
+ * block's start, or equal to total_len, needs no decode.  Errors as kolm_reader_line_spans (an
+ * offset above total_len: KOLM_EARG, the message naming the entry). */
+int kolm_reader_line_of(kolm_reader* r, const uint64_t* offs, uint32_t n, uint64_t* lines, kolm_lines_stats* stats);
+/* The line index while encoding (default off, or KOLM_LINES=1 at context creation with
+ * KOLM_LINES_DELIM = the delimiter as a decimal byte value, default 10): when enabled,
+ * kolm_encode_blocks, kolm_encode_blocks_device, kolm_encode_blocks_device_var and every device
+ * batch of kolm_compress_fixed run k_delim_count once over the batch's resident input, where the
+ * CRC pass of kolm_ctx_set_checksums is launched; the counts come back behind the batch's own final
+ * synchronisation.  The contexts of kolm_encode_blocks_multi ignore the switch.  Disabled: no extra
+ * launch, allocation or synchronisation.  The container's bytes do not depend on the switch. */
+int kolm_ctx_set_lines(kolm_ctx* ctx, int enable, uint32_t delim);
+int kolm_set_lines(int enable, uint32_t delim);  /* default context */
+/* The counts of the last encode call of ctx (NULL: the default context), in container block order:
+ * *nblocks (optional) their count (0 when the call ran with the switch off), *delim (optional) the
+ * delimiter, counts[0, cap) (optional; KOLM_ECAP when cap < the count). */
+int kolm_ctx_lines(kolm_ctx* ctx, uint32_t* counts, uint32_t cap, uint32_t* nblocks, uint32_t* delim);
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (kolm_comm.cpp) ------------- */
 /* The only data exchange of the multi-GPU path: blocks are independent (PY:2350-2369), so

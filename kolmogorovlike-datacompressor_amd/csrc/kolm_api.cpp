@@ -209,6 +209,31 @@ struct kolm_ctx {
         bool launched = false;
         hipEvent_t ev[3] = {};  // kernel start, kernel end, words on the host
     } crc;
+    // line index (kolm_ctx_set_lines; KOLM_LINES=1, KOLM_LINES_DELIM): every encode batch counts the
+    // bytes equal to lines_delim in its blocks on the resident text (lines_prepare / lines_launch /
+    // lines_collect below: the CRC pass's shape, launched where that pass is); clines accumulates
+    // over the batches of one call.  The rest is the state of one counting pass, used by every
+    // caller under the context lock.
+    bool lines = false;
+    u32 lines_delim = 0x0A;
+    std::vector<u32> clines;
+    struct LinePass {
+        u32* h_cnt = nullptr;  // pinned landing buffer of the counts
+        size_t h_cap = 0;
+        std::vector<u32> hb, scan, pbase;  // block bounds, the scans of the run and of the piece counts (nb + 1 each)
+        u32 nb = 0;
+        const u8* text = nullptr;
+        u64 N = 0;
+        u32 bs = 0, delim = 0;
+        bool var = false;
+        bool pieces = false;    // also the 4 KiB pieces' counts ("lin_pcnt", at "lin_pbase") and their scan
+        const lin::Query* q = nullptr;  // with pieces: the queries answered behind the scan
+        u32 nq = 0;
+        u32* dcnt = nullptr;
+        bool armed = false;     // prepared, not launched yet
+        bool launched = false;
+        hipEvent_t ev[3] = {};  // kernel start, kernel end, counts on the host
+    } lin;
     // Lyndon fast route (kolm_ctx_lyndon_report): the last batch's block count, whether the fast
     // route ran and the stream it ran on; the route words stay in the "lyn_route" buffer
     u32 lyn_nb = 0;
@@ -1054,6 +1079,7 @@ int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
                  const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
                  kolm_stats* stats);
 void crc_launch(kolm_ctx* c, hipStream_t s);  // checksums: the prepared CRC pass, if one is armed (below)
+void lines_launch(kolm_ctx* c, hipStream_t s);  // line index: the prepared counting pass, if one is armed (below)
 int decode_blocks_host(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
                        const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap, bool with_crc,
                        const uint32_t* expect, uint32_t* got);  // kolm_decode_blocks[_crc] (with the verify step below)
@@ -1122,6 +1148,7 @@ int encode_each(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bound
     // checksums on: the armed CRC pass goes behind ev[0] on the index stream, so the sort stream
     // (which waits for ev[0] alone) starts without it and the pass runs beside its chain
     crc_launch(c, ms);
+    lines_launch(c, ms);  // line index on: the armed counting pass, in the same place
     // Re-Pair (candidate 9): persistent workgroups (one per block) on their own stream,
     // launched first so they take their CUs while the sort / LZ77 chains queue beside them
     const bool want_rp = (mask >> KOLM_M_REPAIR) & 1u;
@@ -1512,6 +1539,8 @@ int ctx_create(int device, kolm_ctx** out) {
         c->verify = getenv("KOLM_VERIFY") && atoi(getenv("KOLM_VERIFY")) != 0;
         c->dedup = getenv("KOLM_DEDUP") && atoi(getenv("KOLM_DEDUP")) != 0;
         c->checksums = getenv("KOLM_CHECKSUMS") && atoi(getenv("KOLM_CHECKSUMS")) != 0;
+        c->lines = getenv("KOLM_LINES") && atoi(getenv("KOLM_LINES")) != 0;
+        if (const char* e = getenv("KOLM_LINES_DELIM")) c->lines_delim = (u32)atoi(e) & 0xFFu;
         for (auto& e : c->evj) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evr) KOLM_HIP_CHECK(hipEventCreate(&e));
         for (auto& e : c->evg) KOLM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1536,6 +1565,7 @@ kolm_ctx* need_default() {
 void verify_begin(kolm_ctx* c, u32 first_block = 0) {
     c->drep = kolm_dedup_report{};  // the dedup report covers this call's batches too (zero when off)
     c->ccrc.clear();                // and the checksums (none when off)
+    c->clines.clear();              // and the line index
     if (!c->verify) return;
     c->vrep = kolm_verify_report{};
     c->vshard = first_block;
@@ -1657,6 +1687,9 @@ int kolm_ctx_destroy(kolm_ctx* c) {
             if (e) KOLM_HIP_CHECK(hipEventDestroy(e));
         if (c->crc.d_tab) KOLM_HIP_CHECK(hipFree(c->crc.d_tab));
         if (c->crc.h_raw) KOLM_HIP_CHECK(hipHostFree(c->crc.h_raw));
+        for (auto& e : c->lin.ev)
+            if (e) KOLM_HIP_CHECK(hipEventDestroy(e));
+        if (c->lin.h_cnt) KOLM_HIP_CHECK(hipHostFree(c->lin.h_cnt));
         KOLM_HIP_CHECK(hipHostFree(c->h_cnt));
         if (c->h_rt) KOLM_HIP_CHECK(hipHostFree(c->h_rt));
         if (c->h_tail) KOLM_HIP_CHECK(hipHostFree(c->h_tail));
@@ -2191,6 +2224,7 @@ int kolm_encode_blocks_multi(int ngpu, const uint8_t* data, uint64_t total, uint
             c->verify = verify;
             c->dedup = dedup;
             c->checksums = false;  // the multi-device contexts ignore the switch (kolm.h)
+            c->lines = false;      // and the line index's
             verify_begin(c, b0[r]);
             int rc = encode_batch(c, d, n, block_size, nullptr, 0, cand_mask & KOLM_FULL_MASK,
                                   force_method ? force_method + b0[r] : nullptr, arena, dcap,
@@ -2902,6 +2936,134 @@ double crc_blocks_at(kolm_ctx* c, const u8* d, const u32* lens, u32 n, u32* out)
     return crc_collect(c, out);
 }
 
+// ---- line index: delimiter counts of resident bytes (lines_core.h, k_lines.hip) ----
+// One counting pass over the nb blocks of d_text, the CRC pass's shape: lines_prepare makes every
+// allocation and host array, lines_launch puts the stream work on s (the counts are zeroed,
+// computed and copied to pinned host memory behind each other, no host wait), lines_collect hands
+// them out.  pieces (variable geometry only): k_delim_count also writes the 4 KiB pieces' counts
+// and launch_find_scan scans them; then the nq queries q (alive until the collect; block = the
+// block's number in this pass) are answered by k_delim_query behind the scan and their results
+// come back with the counts, in the same copy.  One pass at a time per context (its lock is held).
+void lines_prepare(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* hb, u32 nb, u32 delim, bool pieces,
+                   const lin::Query* q = nullptr, u32 nq = 0) {
+    kolm_ctx::LinePass& p = c->lin;
+    for (auto& e : p.ev)
+        if (!e) KOLM_HIP_CHECK(hipEventCreate(&e));
+    const size_t words = (size_t)nb + nq;
+    if (p.h_cap < words) {
+        if (p.h_cnt) KOLM_HIP_CHECK(hipHostFree(p.h_cnt));
+        p.h_cnt = nullptr;
+        p.h_cap = 0;
+        const size_t cap = std::max<size_t>(words + (words >> 2), 1024);
+        KOLM_HIP_CHECK(hipHostMalloc((void**)&p.h_cnt, cap * sizeof(u32), hipHostMallocDefault));
+        p.h_cap = cap;
+    }
+    p.nb = nb, p.nq = nq, p.q = q;
+    p.launched = false;
+    p.armed = false;
+    p.delim = delim & 0xFFu;
+    p.pieces = pieces && hb != nullptr;
+    p.hb.assign((size_t)nb + 1, 0);
+    for (u32 b = 0; b <= nb; ++b) p.hb[b] = hb ? hb[b] : (u32)std::min<u64>(N, (u64)b * bs);
+    if (nb == 0 || N == 0) return;  // empty blocks alone: every count is 0
+    p.text = d_text, p.N = N, p.bs = bs, p.var = hb != nullptr;
+    p.dcnt = c->get<u32>("lin_cnt", words);
+    if (hb) {  // variable geometry: the blocks' run counts differ
+        p.scan.assign((size_t)nb + 1, 0);
+        for (u32 b = 0; b < nb; ++b) p.scan[b + 1] = p.scan[b] + (u32)ddp::runs(p.hb[b + 1] - p.hb[b]);
+        c->get<u32>("lin_vb", (size_t)nb + 1);
+        c->get<u32>("lin_scan", (size_t)nb + 1);
+    }
+    if (p.pieces) {
+        p.pbase.assign((size_t)nb + 1, 0);
+        for (u32 b = 0; b < nb; ++b) p.pbase[b + 1] = p.pbase[b] + (u32)ddp::pieces(p.hb[b + 1] - p.hb[b]);  // < 2^19 + nb
+        c->get<u32>("lin_pbase", (size_t)nb + 1);
+        c->get<u32>("lin_pcnt", p.pbase[nb]);
+        c->get<u64>("lin_pscan", (size_t)p.pbase[nb] + 2);  // the scan, its total, the column sum
+        if (nq) c->get<lin::Query>("lin_q", nq);
+    }
+    p.armed = true;
+}
+
+// The prepared pass's stream work on s, if one is armed: launches and asynchronous copies only, no
+// allocation and no host wait (encode_each calls it between its own launches).
+void lines_launch(kolm_ctx* c, hipStream_t s) {
+    kolm_ctx::LinePass& p = c->lin;
+    if (!p.armed) return;
+    p.armed = false;
+    const u32 nb = p.nb;
+    KOLM_HIP_CHECK(hipMemsetAsync(p.dcnt, 0, sizeof(u32) * nb, s));
+    Geom geo;
+    const u32* dscan = nullptr;
+    u64 nruns = 0;
+    if (p.var) {  // base / end need the bounds alone
+        geo = Geom{};
+        geo.N = p.N, geo.nb = nb;
+        geo.bs = 1;
+        for (u32 b = 0; b < nb; ++b) geo.bs = std::max(geo.bs, p.hb[b + 1] - p.hb[b]);
+        u32* dvb = c->get<u32>("lin_vb", (size_t)nb + 1);
+        u32* d = c->get<u32>("lin_scan", (size_t)nb + 1);
+        KOLM_HIP_CHECK(hipMemcpyAsync(dvb, p.hb.data(), sizeof(u32) * ((size_t)nb + 1), hipMemcpyHostToDevice, s));
+        KOLM_HIP_CHECK(hipMemcpyAsync(d, p.scan.data(), sizeof(u32) * ((size_t)nb + 1), hipMemcpyHostToDevice, s));
+        geo.vb = dvb, geo.hvb = p.hb.data();
+        dscan = d;
+        nruns = p.scan[nb];
+    } else {
+        geom_init(geo, p.N, p.bs);
+        nruns = (u64)nb * ddp::runs(p.bs);
+    }
+    u32 *dpbase = nullptr, *dpcnt = nullptr;
+    u64* dpscan = nullptr;
+    lin::Query* dq = nullptr;
+    if (p.pieces) {
+        dpbase = c->get<u32>("lin_pbase", (size_t)nb + 1);
+        dpcnt = c->get<u32>("lin_pcnt", p.pbase[nb]);
+        dpscan = c->get<u64>("lin_pscan", (size_t)p.pbase[nb] + 2);
+        KOLM_HIP_CHECK(hipMemcpyAsync(dpbase, p.pbase.data(), sizeof(u32) * ((size_t)nb + 1), hipMemcpyHostToDevice, s));
+        if (p.nq) {
+            dq = c->get<lin::Query>("lin_q", p.nq);
+            KOLM_HIP_CHECK(hipMemcpyAsync(dq, p.q, sizeof(lin::Query) * p.nq, hipMemcpyHostToDevice, s));
+        }
+    }
+    KOLM_HIP_CHECK(hipEventRecord(p.ev[0], s));
+    launch_delim_count(p.text, geo, dscan, nruns, p.delim, dpbase, dpcnt, p.dcnt, s);
+    if (p.pieces) {
+        const u32 npc = p.pbase[nb];
+        launch_find_scan(dpcnt, npc, 0, dpscan + npc + 1, dpscan, s);
+        if (p.nq) launch_delim_query(p.text, geo, p.delim, dpbase, dpscan, dq, p.nq, p.dcnt + nb, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(p.ev[1], s));
+    KOLM_HIP_CHECK(hipMemcpyAsync(p.h_cnt, p.dcnt, sizeof(u32) * ((size_t)nb + (p.pieces ? p.nq : 0)), hipMemcpyDeviceToHost, s));
+    KOLM_HIP_CHECK(hipEventRecord(p.ev[2], s));
+    p.launched = true;
+}
+
+// The counts of the pass enqueued last: out[0, nb), and its queries' results: res[0, nq).  Waits
+// for the read-back's event.  Returns the kernels' device time and, with timing on, adds the
+// counting launch to the per-kernel table.
+double lines_collect(kolm_ctx* c, u32* out, u32* res = nullptr) {
+    kolm_ctx::LinePass& p = c->lin;
+    double ms = 0.0;
+    if (p.launched) {
+        KOLM_HIP_CHECK(hipEventSynchronize(p.ev[2]));
+        ms = ev_ms(p.ev[0], p.ev[1]);
+        if (c->timing) {
+            kolm_ctx::Acc& a = c->kacc[p.pieces ? "k_delim_count+query" : "k_delim_count"];
+            a.fam = KOLM_KT_EMIT;
+            a.strm = 0;
+            a.ms += ms;
+            a.launches += 1;
+            a.bytes += p.hb[p.nb];
+        }
+    }
+    for (u32 b = 0; b < p.nb; ++b) out[b] = p.launched ? p.h_cnt[b] : 0u;
+    // without a launch (empty blocks alone) a RANK is 0 and a SELECT finds nothing
+    for (u32 i = 0; res && i < p.nq; ++i)
+        res[i] = p.launched && p.pieces ? p.h_cnt[p.nb + i] : p.q[i].op == lin::OP_RANK ? 0u : lin::NONE;
+    p.launched = false;
+    return ms;
+}
+
 void checksum_message(u32 block, u32 method, u32 expected, u32 got) {
     char msg[160];
     snprintf(msg, sizeof msg, "checksum: block %u (method %u): expected CRC-32 %08x, got %08x", block, method, expected, got);
@@ -3221,6 +3383,11 @@ struct kolm_reader {
     u8* dpay = nullptr;
     // the blocks' expected CRC-32 (kolm_reader_set_checksums): nb words, or empty = reads are not checked
     std::vector<u32> crcs;
+    // the line index (kolm_reader_set_lines / kolm_reader_index_lines): the blocks' counts of bytes
+    // equal to ldelim, nb words, when has_lines
+    bool has_lines = false;
+    u32 ldelim = 0x0A;
+    std::vector<u32> lcounts;
     // the result of the last kolm_reader_find: absolute offsets and pattern indices, in
     // (offset, pattern) order (kolm_reader_find_copy)
     std::vector<u64> f_offs;
@@ -3374,7 +3541,7 @@ int encode_dedup(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
 int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bounds, u32 nbv, u32 mask,
                  const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
                  kolm_stats* stats) {
-    if (!c->checksums)
+    if (!c->checksums && !c->lines)
         return encode_dedup(c, d_text, N, bs, h_bounds, nbv, mask, h_force, d_arena, arena_cap, h_sizes, h_method, h_off,
                             stats);
     // the geometry checks of encode_each before the first launch
@@ -3385,17 +3552,28 @@ int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
     }
     const u64 n = h_bounds ? h_bounds[nbv] : N;
     const u32 nb = h_bounds ? nbv : (u32)((N + bs - 1) / bs);
-    crc_prepare(c, d_text, n, bs, h_bounds, nb);
+    if (c->checksums) crc_prepare(c, d_text, n, bs, h_bounds, nb);
+    // the line index's counting pass (kolm_ctx_set_lines): prepared and launched as the CRC pass is
+    if (c->lines) lines_prepare(c, d_text, n, bs, h_bounds, nb, c->lines_delim, false);
     struct Disarm {  // an error return or a throw before the batch's first launch: nothing was enqueued
         kolm_ctx* c;
-        ~Disarm() { c->crc.armed = false; }
+        ~Disarm() { c->crc.armed = c->lin.armed = false; }
     } disarm{c};
     const int rc = encode_dedup(c, d_text, N, bs, h_bounds, nbv, mask, h_force, d_arena, arena_cap, h_sizes, h_method,
                                 h_off, stats);
-    const size_t at = c->ccrc.size();
-    c->ccrc.resize(at + nb);
-    crc_collect(c, c->ccrc.data() + at);
-    if (rc && rc != KOLM_EVERIFY) c->ccrc.resize(at);  // the batch was not encoded
+    const bool encoded = !rc || rc == KOLM_EVERIFY;  // else the batch was not encoded
+    if (c->checksums) {
+        const size_t at = c->ccrc.size();
+        c->ccrc.resize(at + nb);
+        crc_collect(c, c->ccrc.data() + at);
+        if (!encoded) c->ccrc.resize(at);
+    }
+    if (c->lines) {
+        const size_t at = c->clines.size();
+        c->clines.resize(at + nb);
+        lines_collect(c, c->clines.data() + at);
+        if (!encoded) c->clines.resize(at);
+    }
     return rc;
 }
 
@@ -4606,6 +4784,424 @@ int kolm_reader_set_checksums(kolm_reader* r, const uint32_t* crc_in, uint32_t n
         return KOLM_EARG;
     }
     r->crcs.assign(crc_in, crc_in + nblocks);
+    return KOLM_OK;
+}
+
+}  // extern "C"
+
+// ---- line index: lines of a container on the device (lines_core.h, k_lines.hip, kolm_lines.cpp) ----
+namespace {
+
+// every selected block must be one the device decodes (as reads and searches check)
+int lines_check_blocks(kolm_reader* r, const RangePlan& p, kolm_lines_stats& st) {
+    st.blocks_decoded = (u32)p.sel.size();
+    st.groups = (u32)p.group_first.size() - 1;
+    for (u32 b : p.sel) {
+        const u32 m = r->methods[b];
+        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
+            r->lens[b] >= (1u << 31)) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        st.bytes_decoded += r->lens[b];
+    }
+    return KOLM_OK;
+}
+
+// Group g of the plan decoded into the "rd_dec" scratch (its blocks back to back; w.gl their
+// lengths), as a read decodes it: payload runs, compaction, decode_batch, then the status and
+// checksum checks before anything else looks at the bytes.  The caller holds the context's lock.
+struct GroupDec {
+    std::vector<u32> gm, gl, status, scan, words;
+    std::vector<u64> gp;
+    std::vector<rng::Seg> runs;
+};
+int lines_decode_group(kolm_reader* r, const RangePlan& p, u32 g, GroupDec& w, u8*& dec, u64& tot, kolm_lines_stats& st) {
+    kolm_ctx* c = r->c;
+    const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
+    w.gm.resize(n), w.gl.resize(n), w.gp.assign((size_t)n + 1, 0);
+    w.runs.clear();
+    tot = 0;
+    for (u32 i = i0; i < i1; ++i) {
+        const u32 b = p.sel[i];
+        w.gm[i - i0] = r->methods[b];
+        w.gl[i - i0] = r->lens[b];
+        tot += r->lens[b];
+        const u64 plen = r->poff[b + 1] - r->poff[b];
+        if (i == i0 || b != p.sel[i - 1] + 1) w.runs.push_back(rng::Seg{r->poff[b] - r->poff[0], w.gp[i - i0], 0});
+        w.runs.back().len += plen;
+        w.gp[i - i0 + 1] = w.gp[i - i0] + plen;
+    }
+    const u8* pay = r->dpay + w.runs[0].src;
+    if (w.runs.size() > 1) {  // as reads do: several payload runs are gathered first
+        u8* stage = c->get<u8>("rd_pay", w.gp[n] + 64);
+        gather_segments(c, "rd_c", r->dpay, stage, w.runs.data(), (u32)w.runs.size(), w.scan, c->ev[4], c->ev[5]);
+        pay = stage;
+    }
+    dec = c->get<u8>("rd_dec", tot + 64 + rng::WORD);
+    double ms = 0.0;
+    if (int e = decode_batch(c, pay, w.gp.data(), w.gm.data(), w.gl.data(), n, tot, dec, &ms, &w.status)) return e;
+    st.ms_decode += ms;
+    for (u32 i = 0; i < n; ++i)
+        if (w.status[i]) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], w.gm[i],
+                     w.status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
+            set_err(msg);
+            return KOLM_EARG;
+        }
+    if (!r->crcs.empty()) {
+        w.words.resize(n);
+        crc_blocks_at(c, dec, w.gl.data(), n, w.words.data());
+        for (u32 i = 0; i < n; ++i) {
+            const u32 b = p.sel[i0 + i];
+            if (w.words[i] != r->crcs[b]) {
+                checksum_message(b, w.gm[i], r->crcs[b], w.words[i]);
+                return KOLM_ECHECKSUM;
+            }
+        }
+    }
+    return KOLM_OK;
+}
+
+void lines_message(u32 block, u32 expected, u32 got) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "line index: block %u: expected %u delimiters, got %u", block, expected, got);
+    set_err(msg);
+}
+
+// The plan whose selected blocks are `blocks` (ascending, distinct, none empty), grouped as a
+// read's blocks are: one 1-byte range at each block's start.
+int lines_plan(kolm_reader* r, const std::vector<u32>& blocks, RangePlan& p) {
+    std::vector<u64> offs(blocks.size()), lens(blocks.size(), 1);
+    for (size_t i = 0; i < blocks.size(); ++i) offs[i] = r->starts[blocks[i]];
+    return range_plan(r->lens.data(), r->starts.data(), r->nb, offs.data(), lens.data(), (u32)blocks.size(), 0, p);
+}
+
+// The queries q (sorted by block; q[i].block = the container's block, never an empty one) answered
+// group by group: res[i].  Each group's real counts are compared with the attached index first.
+int lines_run(kolm_reader* r, std::vector<lin::Query>& q, std::vector<u32>& res, kolm_lines_stats& st) {
+    st.queries = (u32)q.size();
+    res.assign(q.size(), 0);
+    if (q.empty()) return KOLM_OK;
+    std::vector<u32> blocks, cb(q.size());  // cb: the queries' container block numbers
+    for (size_t i = 0; i < q.size(); ++i) {
+        cb[i] = q[i].block;
+        if (blocks.empty() || blocks.back() != cb[i]) blocks.push_back(cb[i]);
+    }
+    RangePlan p;
+    if (int rc = lines_plan(r, blocks, p)) return rc;
+    if (int rc = lines_check_blocks(r, p, st)) return rc;
+    kolm_ctx* c = r->c;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        c->active = c->stream;
+        GroupDec w;
+        std::vector<u32> hb, cnt;
+        size_t q0 = 0;
+        for (u32 gi = 0; gi + 1 < p.group_first.size(); ++gi) {
+            const u32 i0 = p.group_first[gi], i1 = p.group_first[gi + 1], n = i1 - i0;
+            u8* dec = nullptr;
+            u64 tot = 0;
+            if (int e = lines_decode_group(r, p, gi, w, dec, tot, st)) return e;
+            // the group's queries: q[q0, q1), their blocks renumbered to the group's slots
+            size_t q1 = q0;
+            u32 slot = 0;
+            while (q1 < q.size() && cb[q1] <= p.sel[i1 - 1]) {
+                while (p.sel[i0 + slot] != cb[q1]) ++slot;
+                q[q1++].block = slot;
+            }
+            hb.assign((size_t)n + 1, 0);
+            for (u32 i = 0; i < n; ++i) hb[i + 1] = hb[i] + w.gl[i];
+            cnt.resize(n);
+            lines_prepare(c, dec, tot, 0, hb.data(), n, r->ldelim, true, q.data() + q0, (u32)(q1 - q0));
+            lines_launch(c, c->stream);
+            st.ms_lines += lines_collect(c, cnt.data(), res.data() + q0);
+            for (u32 i = 0; i < n; ++i)
+                if (cnt[i] != r->lcounts[p.sel[i0 + i]]) {
+                    lines_message(p.sel[i0 + i], r->lcounts[p.sel[i0 + i]], cnt[i]);
+                    return KOLM_ELINES;
+                }
+            for (size_t i = q0; i < q1; ++i)
+                if (res[i] == lin::NONE) {
+                    lines_message(cb[i], r->lcounts[cb[i]], cnt[q[i].block]);
+                    return KOLM_ELINES;
+                }
+            q0 = q1;
+        }
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        return KOLM_OK;
+    });
+}
+
+int lines_need_index(const char* who, kolm_reader* r) {
+    if (r->has_lines) return KOLM_OK;
+    set_err(std::string(who) + ": no line index is attached (kolm_reader_set_lines / kolm_reader_index_lines)");
+    return KOLM_EARG;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kolm_delim_count_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks, uint32_t delim,
+                            uint32_t* counts, double* ms) {
+    if (!c) return KOLM_EARG;
+    if (ms) *ms = 0.0;
+    if (nblocks == 0) return KOLM_OK;
+    if (!h_bounds || !counts) return KOLM_EARG;
+    if (delim > 0xFFu) {
+        set_err("the delimiter is one byte value");
+        return KOLM_EARG;
+    }
+    if (h_bounds[0] != 0) {
+        set_err("block bounds must start at 0");
+        return KOLM_EARG;
+    }
+    std::vector<u32> hb((size_t)nblocks + 1, 0);
+    for (u32 b = 0; b < nblocks; ++b) {
+        if (h_bounds[b + 1] < h_bounds[b] || h_bounds[b + 1] >= (1ull << 31)) {
+            set_err("blocks must be contiguous, the batch smaller than 2^31 bytes");
+            return KOLM_EARG;
+        }
+        hb[b + 1] = (u32)h_bounds[b + 1];
+    }
+    if (hb[nblocks] && !d_data) return KOLM_EARG;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        lines_prepare(c, static_cast<const u8*>(d_data), hb[nblocks], 0, hb.data(), nblocks, delim, false);
+        lines_launch(c, c->stream);
+        const double t = lines_collect(c, counts);
+        if (ms) *ms = t;
+        return KOLM_OK;
+    });
+}
+
+int kolm_delim_count_pieces_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks, uint32_t delim,
+                                   uint32_t* counts, uint32_t* piece_counts, uint64_t cap, double* ms) {
+    if (!c) return KOLM_EARG;
+    if (ms) *ms = 0.0;
+    if (nblocks == 0) return KOLM_OK;
+    if (!h_bounds || !counts || !piece_counts || delim > 0xFFu || h_bounds[0] != 0) return KOLM_EARG;
+    std::vector<u32> hb((size_t)nblocks + 1, 0);
+    u64 npc = 0;
+    for (u32 b = 0; b < nblocks; ++b) {
+        if (h_bounds[b + 1] < h_bounds[b] || h_bounds[b + 1] >= (1ull << 31)) {
+            set_err("blocks must be contiguous, the batch smaller than 2^31 bytes");
+            return KOLM_EARG;
+        }
+        hb[b + 1] = (u32)h_bounds[b + 1];
+        npc += ddp::pieces(hb[b + 1] - hb[b]);
+    }
+    if (cap < npc) {
+        set_err("kolm_delim_count_pieces_device: capacity too small");
+        return KOLM_ECAP;
+    }
+    if (hb[nblocks] && !d_data) return KOLM_EARG;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        lines_prepare(c, static_cast<const u8*>(d_data), hb[nblocks], 0, hb.data(), nblocks, delim, true);
+        lines_launch(c, c->stream);
+        const double t = lines_collect(c, counts);
+        if (npc && hb[nblocks])  // the stream is drained: the collect waited for the counts' copy behind the kernels
+            KOLM_HIP_CHECK(hipMemcpy(piece_counts, c->get<u32>("lin_pcnt", npc), sizeof(u32) * npc, hipMemcpyDeviceToHost));
+        if (ms) *ms = t;
+        return KOLM_OK;
+    });
+}
+
+int kolm_reader_set_lines(kolm_reader* r, uint32_t delim, const uint32_t* counts, uint32_t nblocks) {
+    if (!r || !r->c) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(r->c->mu);
+    if (!counts) {
+        r->has_lines = false;
+        r->lcounts.clear();
+        return KOLM_OK;
+    }
+    if (delim > 0xFFu) {
+        set_err("kolm_reader_set_lines: the delimiter is one byte value");
+        return KOLM_EARG;
+    }
+    if (nblocks != r->nb) {
+        set_err("kolm_reader_set_lines: the block count differs from the container's");
+        return KOLM_EARG;
+    }
+    r->lcounts.assign(counts, counts + nblocks);
+    r->ldelim = delim;
+    r->has_lines = true;
+    return KOLM_OK;
+}
+
+int kolm_reader_index_lines(kolm_reader* r, uint32_t delim, uint32_t* counts, uint32_t cap, kolm_lines_stats* stats) {
+    if (stats) *stats = kolm_lines_stats{};
+    if (!r || !r->c) return KOLM_EARG;
+    if (delim > 0xFFu) {
+        set_err("kolm_reader_index_lines: the delimiter is one byte value");
+        return KOLM_EARG;
+    }
+    if (counts && cap < r->nb) {
+        set_err("kolm_reader_index_lines: capacity too small");
+        return KOLM_ECAP;
+    }
+    kolm_lines_stats st{};
+    RangePlan p;
+    const u64 lo = 0, len = r->total;
+    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, &lo, &len, 1, 0, p)) return rc;
+    if (int rc = lines_check_blocks(r, p, st)) return rc;
+    std::vector<u32> all(r->nb, 0);
+    kolm_ctx* c = r->c;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (p.sel.empty()) return KOLM_OK;
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        c->active = c->stream;
+        GroupDec w;
+        std::vector<u32> hb, cnt;
+        for (u32 gi = 0; gi + 1 < p.group_first.size(); ++gi) {
+            const u32 i0 = p.group_first[gi], n = p.group_first[gi + 1] - i0;
+            u8* dec = nullptr;
+            u64 tot = 0;
+            if (int e = lines_decode_group(r, p, gi, w, dec, tot, st)) return e;
+            hb.assign((size_t)n + 1, 0);
+            for (u32 i = 0; i < n; ++i) hb[i + 1] = hb[i] + w.gl[i];
+            cnt.resize(n);
+            lines_prepare(c, dec, tot, 0, hb.data(), n, delim, false);
+            lines_launch(c, c->stream);
+            st.ms_lines += lines_collect(c, cnt.data());
+            for (u32 i = 0; i < n; ++i) all[p.sel[i0 + i]] = cnt[i];
+        }
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        return KOLM_OK;
+    });
+    if (stats) *stats = st;
+    if (rc) return rc;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->lcounts = all;
+        r->ldelim = delim;
+        r->has_lines = true;
+    }
+    if (counts) std::copy(all.begin(), all.end(), counts);
+    return KOLM_OK;
+}
+
+int kolm_reader_line_spans(kolm_reader* r, const uint64_t* lines, uint32_t n, uint64_t* starts, uint64_t* ends,
+                           kolm_lines_stats* stats) {
+    if (stats) *stats = kolm_lines_stats{};
+    if (!r || !r->c || (n && (!lines || !starts || !ends))) return KOLM_EARG;
+    if (int rc = lines_need_index("kolm_reader_line_spans", r)) return rc;
+    // every argument check before the first launch: the lines, the selected blocks
+    std::vector<u64> prefix;
+    lines_prefix(r->lcounts.data(), r->nb, prefix);
+    const u64 D = prefix[r->nb];
+    std::vector<u64> need;  // the delimiters whose positions the spans are made of, each once
+    for (u32 i = 0; i < n; ++i) {
+        if (lines[i] > D) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "kolm_reader_line_spans: entry %u: line %llu of %llu", i, (unsigned long long)lines[i],
+                     (unsigned long long)(D + 1));
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        if (lines[i] > 0) need.push_back(lines[i] - 1);
+        if (lines[i] < D) need.push_back(lines[i]);
+    }
+    std::sort(need.begin(), need.end());
+    need.erase(std::unique(need.begin(), need.end()), need.end());
+    std::vector<lin::Query> q(need.size());  // ascending delimiter numbers: sorted by block
+    for (size_t i = 0; i < need.size(); ++i) {
+        const u32 b = lines_block_of(prefix, need[i]);
+        q[i] = lin::Query{b, (u32)(need[i] - prefix[b]), lin::OP_SELECT};
+    }
+    const std::vector<lin::Query> asked = q;
+    kolm_lines_stats st{};
+    std::vector<u32> res;
+    const int rc = lines_run(r, q, res, st);
+    if (stats) *stats = st;
+    if (rc) return rc;  // no results leave a failed call
+    auto pos = [&](u64 k) {
+        const size_t i = (size_t)(std::lower_bound(need.begin(), need.end(), k) - need.begin());
+        return r->starts[asked[i].block] + res[i];
+    };
+    for (u32 i = 0; i < n; ++i) {
+        starts[i] = lines[i] ? pos(lines[i] - 1) + 1 : 0;
+        ends[i] = lines[i] < D ? pos(lines[i]) : r->total;
+    }
+    return KOLM_OK;
+}
+
+int kolm_reader_line_of(kolm_reader* r, const uint64_t* offs, uint32_t n, uint64_t* lines, kolm_lines_stats* stats) {
+    if (stats) *stats = kolm_lines_stats{};
+    if (!r || !r->c || (n && (!offs || !lines))) return KOLM_EARG;
+    if (int rc = lines_need_index("kolm_reader_line_of", r)) return rc;
+    std::vector<u64> prefix;
+    lines_prefix(r->lcounts.data(), r->nb, prefix);
+    // (block, offset in it) of every offset that needs a decode, each once, sorted by block
+    std::vector<std::pair<u32, u32>> at(n), need;
+    for (u32 i = 0; i < n; ++i) {
+        if (offs[i] > r->total) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "kolm_reader_line_of: entry %u: offset %llu is not inside the container's %llu bytes", i,
+                     (unsigned long long)offs[i], (unsigned long long)r->total);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        const u32 b = offs[i] == r->total
+                          ? r->nb
+                          : (u32)(std::upper_bound(r->starts.begin(), r->starts.end(), offs[i]) - r->starts.begin()) - 1;
+        at[i] = {b, (u32)(offs[i] - r->starts[b])};
+        if (at[i].second) need.push_back(at[i]);  // a block's start, the stream's end: the prefix sum alone
+    }
+    std::sort(need.begin(), need.end());
+    need.erase(std::unique(need.begin(), need.end()), need.end());
+    std::vector<lin::Query> q(need.size());
+    for (size_t i = 0; i < need.size(); ++i) q[i] = lin::Query{need[i].first, need[i].second, lin::OP_RANK};
+    kolm_lines_stats st{};
+    std::vector<u32> res;
+    const int rc = lines_run(r, q, res, st);
+    if (stats) *stats = st;
+    if (rc) return rc;
+    for (u32 i = 0; i < n; ++i) {
+        lines[i] = prefix[at[i].first];
+        if (at[i].second) lines[i] += res[(size_t)(std::lower_bound(need.begin(), need.end(), at[i]) - need.begin())];
+    }
+    return KOLM_OK;
+}
+
+int kolm_ctx_set_lines(kolm_ctx* c, int enable, uint32_t delim) {
+    if (!c || delim > 0xFFu) return KOLM_EARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->lines = enable != 0;
+    c->lines_delim = delim;
+    return KOLM_OK;
+}
+
+int kolm_set_lines(int enable, uint32_t delim) {
+    kolm_ctx* c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    return kolm_ctx_set_lines(c, enable, delim);
+}
+
+int kolm_ctx_lines(kolm_ctx* c, uint32_t* counts, uint32_t cap, uint32_t* nblocks, uint32_t* delim) {
+    if (!c) c = need_default();
+    if (!c) return KOLM_ENOINIT;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (nblocks) *nblocks = (u32)c->clines.size();
+    if (delim) *delim = c->lines_delim;
+    if (counts) {
+        if (cap < c->clines.size()) {
+            set_err("kolm_ctx_lines: capacity too small");
+            return KOLM_ECAP;
+        }
+        std::copy(c->clines.begin(), c->clines.end(), counts);
+    }
     return KOLM_OK;
 }
 

@@ -683,6 +683,26 @@ void dedup_expand(const std::vector<u32>& rep, const std::vector<u32>& distinct,
 void launch_crc32(const u8* text, const Geom& geo, const u32* scan, u64 nruns, const u32* tab, u32* raw, hipStream_t s);
 }  // namespace kolm
 
+// ---- k_lines.hip / kolm_lines.cpp: line index (lines_core.h) ----
+#include "lines_core.h"
+namespace kolm {
+// cnt [nb] (zeroed by the caller on s) receives every block's count of bytes equal to delim.
+// scan / nruns as launch_block_fp.  pcnt (optional): the count of every 4 KiB piece, block b's
+// piece k at pcnt[pbase[b] + k] (pbase [nb + 1]: the exclusive scan of the blocks' piece counts,
+// device; every piece is written).  Reads [text, text + geo.N) and nothing else.
+void launch_delim_count(const u8* text, const Geom& geo, const u32* scan, u64 nruns, u32 delim, const u32* pbase, u32* pcnt,
+                        u32* cnt, hipStream_t s);
+// pscan [pieces + 1]: the exclusive scan of pcnt with the total behind it (launch_find_scan with
+// np = 0).  Query i writes res[i]; each reads at most one piece of its block.
+void launch_delim_query(const u8* text, const Geom& geo, u32 delim, const u32* pbase, const u64* pscan, const lin::Query* q,
+                        u32 nq, u32* res, hipStream_t s);
+// the host planner (kolm_lines_locate / kolm_lines_locate_offsets, include/kolm.h)
+// prefix [nb + 1]: the u64 exclusive scan of counts
+void lines_prefix(const u32* counts, u32 nb, std::vector<u64>& prefix);
+// largest b < nb with prefix[b] <= k (k < prefix[nb]): the block of delimiter k, never one without delimiters
+u32 lines_block_of(const std::vector<u64>& prefix, u64 k);
+}  // namespace kolm
+
 // ---- k_find.hip: search of a resident buffer (find_core.h) ----
 #include "find_core.h"
 namespace kolm {

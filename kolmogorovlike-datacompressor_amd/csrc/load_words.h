@@ -1,5 +1,6 @@
 // The block-relative 16-byte words of one item (dedup_core.h), as the kernels that stream a batch
-// block by block read them: k_block_fp and k_dedup_cmp (k_dedup.hip) and k_crc32 (k_crc.hip).
+// block by block read them: k_block_fp and k_dedup_cmp (k_dedup.hip), k_crc32 (k_crc.hip), and
+// k_delim_count and k_delim_query (k_lines.hip).
 // Loads: aligned 16-byte words that lie inside the batch [t0, t1) whole; the words at the batch's
 // two ends whose aligned neighbours would leave it are read byte by byte.  No load touches a byte
 // outside the batch.  Bytes of a word past the block's end are zero.

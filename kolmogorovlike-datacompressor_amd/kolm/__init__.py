@@ -8,7 +8,9 @@ Drop-in for the reference's block API (PY = final_researched/kolm_final_research
     decompress(container) -> bytes                             PY:2451-2550
     open_container(container) -> Reader                        (not in PY: byte ranges of a
                                                                container, only the touched
-                                                               blocks decoded, on the device)
+                                                               blocks decoded, on the device;
+                                                               with lines=: lines of the data,
+                                                               kolm.lines)
     _select_encoders() / _select_decoders()                    PY:2152-2207
     bbwt_forward, mtf_encode, rice_encode, encode_lz77,
     encode_bbwt_mtf_rice, encode_raw, encode_xor,
@@ -41,6 +43,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 from . import _lib
 from ._lib import KolmError, KolmUnavailable, KolmVerifyError  # noqa: F401
 from .checksums import Checksums, KolmChecksumError, as_checksums
+from .lines import KolmLineIndexError, LineIndex, as_line_index, delim_byte
 from .container import (MODE_CDC, MODE_FIXED, read_container, read_toc, uleb128_decode_stream,  # noqa: F401
                         uleb128_encode, write_container)
 from .decode import decode_block
@@ -53,6 +56,7 @@ __all__ = [
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
     "open_container", "Reader", "PatternSet", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
     "Checksums", "KolmChecksumError", "crc32_blocks", "crc32_combine", "last_checksums", "checksums_of", "check",
+    "LineIndex", "KolmLineIndexError", "line_index", "line_index_of", "last_line_index", "last_lines",
 ]
 
 CANDIDATE_NAMES = ["raw", "xor", "bbwt", "bbwt_bp", "bbwt_nib", "bbwt_br", "bbwt_gray", "lz77",
@@ -73,6 +77,10 @@ G_DEDUP: bool = False
 # checksums (not in PY): every device batch takes the CRC-32 of its blocks on the resident input;
 # the container's bytes do not change, the manifest is last_checksums() (kolm.checksums)
 G_CHECKSUMS: bool = False
+# line index (not in PY): every device batch counts the delimiter bytes of its blocks on the resident
+# input; the container's bytes do not change, the index is last_line_index() (kolm.lines).  True
+# (the delimiter b"\n") or a one-byte delimiter
+G_LINES = False
 
 _last_stats: Dict[str, Any] = {}
 
@@ -152,6 +160,71 @@ def _keep_empty(want: bool, mode: int, size_field: int) -> None:
     """Empty input: nothing is launched; with checksums on the manifest is the empty one, not None."""
     global _last_checksums
     _last_checksums = Checksums(mode, size_field, 0, [], []) if want or _lib._ENV_CHECKSUMS else None
+
+
+def _want_lines(lines) -> Optional[int]:
+    """The delimiter byte of an encode call's `lines` argument (None: G_LINES), or None for off."""
+    if lines is None:
+        lines = G_LINES
+    if lines is False:
+        return None
+    return 0x0A if lines is True else delim_byte(lines)
+
+
+_last_line_index: Optional[LineIndex] = None
+
+
+def last_line_index() -> Optional[LineIndex]:
+    """The line index (kolm.lines.LineIndex) of the last encode call of this module when it ran
+    with lines on: every block's delimiter count, taken on the device from the resident input.
+    None when it ran with lines off."""
+    return _last_line_index
+
+
+def _keep_lines(delim: Optional[int], mode: int, size_field: int, data, lens, multi_block_size: Optional[int] = None) -> None:
+    """After an encode call: the index from the counts the call left (kolm_ctx_lines), or, for a
+    multi-device call (its contexts ignore the switch), from one line_index pass."""
+    global _last_line_index
+    _last_line_index = None
+    got = _lib.last_lines_counts()
+    if multi_block_size is not None and (delim is not None or _lib._ENV_LINES):
+        d = _lib._ENV_LINES_DELIM if delim is None else delim
+        got = (d, _lib.delim_counts(data, d, multi_block_size))
+    if got is not None:
+        _last_line_index = LineIndex(mode, size_field, len(data), lens, got[0], got[1])
+
+
+def _keep_empty_lines(delim: Optional[int], mode: int, size_field: int) -> None:
+    """Empty input: nothing is launched; with lines on the index is the empty one, not None."""
+    global _last_line_index
+    if delim is None and _lib._ENV_LINES:
+        delim = _lib._ENV_LINES_DELIM
+    _last_line_index = None if delim is None else LineIndex(mode, size_field, 0, [], delim, [])
+
+
+def line_index(data: bytes, block_size: Optional[int] = None, bounds=None, delim=b"\n", data_offset: int = 0,
+               size_field: int = 0) -> LineIndex:
+    """The line index of data's blocks (fixed blocks of block_size: the index of
+    compress_blocks_fixed(data, block_size); or bounds[i]..bounds[i+1], empty blocks allowed: a CDC
+    index with the given size field, compress_blocks_cdc's avg_size), counted on the device in one
+    streaming pass (k_delim_count).  data_offset (0..15) places the data that many bytes into its
+    device buffer."""
+    d = delim_byte(delim)
+    n = len(data)
+    counts = _lib.delim_counts(data, d, block_size, bounds, data_offset=data_offset)
+    if bounds is None:
+        if not block_size or block_size <= 0:
+            raise ValueError("give a positive block_size or bounds")
+        return LineIndex(MODE_FIXED, block_size, n, [min(block_size, n - i) for i in range(0, n, block_size)], d, counts)
+    bl = [int(x) for x in bounds]
+    return LineIndex(MODE_CDC, size_field, n, [y - x for x, y in zip(bl, bl[1:])], d, counts)
+
+
+def line_index_of(container: bytes, delim=b"\n", checksums=None) -> LineIndex:
+    """The line index of an existing container: every block is decoded on the device and its
+    delimiters counted there (kolm_reader_index_lines); only the counts come back."""
+    with Reader(container, checksums=checksums, lines=delim) as r:
+        return r.line_index
 
 
 def crc32_blocks(data: bytes, block_size: Optional[int] = None, bounds=None, data_offset: int = 0) -> List[int]:
@@ -376,38 +449,45 @@ def candidate_mask(hot_path: bool = False, v2_new: Optional[bool] = None) -> int
 
 def encode_blocks(data: bytes, block_size: int, cand_mask: Optional[int] = None, devices: int = 1,
                   hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None,
-                  dedup: Optional[bool] = None, checksums: Optional[bool] = None):
+                  dedup: Optional[bool] = None, checksums: Optional[bool] = None, lines=None):
     """Batched device MDL over fixed blocks: (method_ids, orig_lens, payloads, sizes).
     devices > 1 shards the blocks over that many GPUs of this process.  `verify` (default
     G_VERIFY): the payloads are decoded and compared with the input on the device before the
     call returns (KolmVerifyError otherwise).  `dedup` (default G_DEDUP): repeated blocks are
     encoded once per device batch (same result; last_dedup()).  `checksums` (default
     G_CHECKSUMS): the blocks' CRC-32 are taken on the device from the resident input
-    (last_checksums(); with devices > 1 from one separate crc32_blocks pass)."""
+    (last_checksums(); with devices > 1 from one separate crc32_blocks pass).  `lines` (default
+    G_LINES; True or a one-byte delimiter): the blocks' delimiter counts are taken the same way
+    (last_line_index())."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
-    global _last_stats, _last_checksums
+    global _last_stats, _last_checksums, _last_line_index
     mask = candidate_mask(hot_path, v2_new) if cand_mask is None else cand_mask
     n = len(data)
     _last_checksums = None
+    _last_line_index = None
+    ld = _want_lines(lines)
     if n == 0:
         _keep_empty(_want_checksums(checksums), MODE_FIXED, block_size)
+        _keep_empty_lines(ld, MODE_FIXED, block_size)
         return [], [], [], None
     if devices > 1:
         sizes, method, payloads, st = _lib.encode_blocks_multi(bytes(data), block_size, devices, mask,
                                                                verify=_want_verify(verify), dedup=_want_dedup(dedup))
     else:
         sizes, method, payloads, st = _lib.encode_blocks(bytes(data), block_size, mask, verify=_want_verify(verify),
-                                                         dedup=_want_dedup(dedup), checksums=_want_checksums(checksums))
+                                                         dedup=_want_dedup(dedup), checksums=_want_checksums(checksums),
+                                                         lines=ld)
     _last_stats = st
     orig = [min(block_size, n - i) for i in range(0, n, block_size)]
     _keep_checksums(_want_checksums(checksums), MODE_FIXED, block_size, data, orig, block_size if devices > 1 else None)
+    _keep_lines(ld, MODE_FIXED, block_size, data, orig, block_size if devices > 1 else None)
     return [int(m) for m in method], orig, payloads, sizes
 
 
 def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1, hot_path: bool = False,
                           v2_new: Optional[bool] = None, verify: Optional[bool] = None,
-                          dedup: Optional[bool] = None, checksums: Optional[bool] = None) -> bytes:
+                          dedup: Optional[bool] = None, checksums: Optional[bool] = None, lines=None) -> bytes:
     """Fixed-size chunking + per-block MDL selection + KOLR container (PY:2332-2445).
     `devices` (not in PY) spreads the blocks over that many GPUs of this process;
     `hot_path` (not in PY) restricts the candidates to ids 0..8; `v2_new` (default
@@ -418,55 +498,66 @@ def compress_blocks_fixed(data: bytes, block_size: int = 8192, devices: int = 1,
     and copies the payload to the repeats: the same container in less time (last_dedup());
     `checksums` (not in PY, default G_CHECKSUMS) takes the CRC-32 of every block on the device
     from the resident input: the same container, and last_checksums() is its manifest (with
-    devices > 1 the manifest comes from one separate crc32_blocks pass over the data)."""
+    devices > 1 the manifest comes from one separate crc32_blocks pass over the data); `lines`
+    (not in PY, default G_LINES; True for b"\n" or a one-byte delimiter) counts that byte in every
+    block the same way: the same container, and last_line_index() is its line index."""
     if block_size <= 0:
         raise ValueError("block_size must be positive")
-    global _last_stats, _last_checksums
+    global _last_stats, _last_checksums, _last_line_index
     _last_checksums = None
+    _last_line_index = None
+    ld = _want_lines(lines)
     n = len(data)
     nb = (n + block_size - 1) // block_size
     if nb > 0xFFFF:
         raise struct.error("'H' format requires 0 <= number <= 65535")
     if devices > 1:
         mids, orig, payloads, _ = encode_blocks(data, block_size, devices=devices, hot_path=hot_path, v2_new=v2_new,
-                                                verify=verify, dedup=dedup, checksums=checksums)
+                                                verify=verify, dedup=dedup, checksums=checksums,
+                                                lines=False if ld is None else ld)
         return write_container(MODE_FIXED, block_size, n, mids, orig, payloads)
     if n == 0:
         _keep_empty(_want_checksums(checksums), MODE_FIXED, block_size)
+        _keep_empty_lines(ld, MODE_FIXED, block_size)
         return write_container(MODE_FIXED, block_size, 0, [], [], [])
     # one native call: staged upload, batched encode, TOC, payloads into the container
     blob, st = _lib.compress_fixed(data, block_size, candidate_mask(hot_path, v2_new), verify=_want_verify(verify),
-                                   dedup=_want_dedup(dedup), checksums=_want_checksums(checksums))
+                                   dedup=_want_dedup(dedup), checksums=_want_checksums(checksums), lines=ld)
     _last_stats = st
-    _keep_checksums(_want_checksums(checksums), MODE_FIXED, block_size, data,
-                    [min(block_size, n - i) for i in range(0, n, block_size)])
+    orig = [min(block_size, n - i) for i in range(0, n, block_size)]
+    _keep_checksums(_want_checksums(checksums), MODE_FIXED, block_size, data, orig)
+    _keep_lines(ld, MODE_FIXED, block_size, data, orig)
     return blob
 
 
 def compress_blocks_cdc(data: bytes, min_size: int = 4096, avg_size: int = 8192, max_size: int = 16384,
                         hot_path: bool = False, v2_new: Optional[bool] = None, verify: Optional[bool] = None,
-                        dedup: Optional[bool] = None, checksums: Optional[bool] = None) -> bytes:
+                        dedup: Optional[bool] = None, checksums: Optional[bool] = None, lines=None) -> bytes:
     """FastCDC chunking + per-block MDL selection + KOLR container in CDC mode
     (PY:2213-2326): boundaries and every candidate on the GPU, one batched device call for
     all chunks (variable block geometry), the TOC on the host.  `hot_path` (not in PY)
-    restricts the candidates to ids 0..8; `verify`, `dedup` and `checksums` as in
+    restricts the candidates to ids 0..8; `verify`, `dedup`, `checksums` and `lines` as in
     compress_blocks_fixed (identical chunks are encoded once; this adds no shift resistance to
     the chunking)."""
-    global _last_stats, _last_checksums
+    global _last_stats, _last_checksums, _last_line_index
     _last_checksums = None
+    _last_line_index = None
+    ld = _want_lines(lines)
     bounds = cdc_fast_boundaries_strict(data, min_size, avg_size, max_size)
     if len(bounds) > 0xFFFF:  # PY packs the block count as '<H' before encoding (PY:2222)
         raise struct.error("'H' format requires 0 <= number <= 65535")
     n = len(data)
     if n == 0:
         _keep_empty(_want_checksums(checksums), MODE_CDC, avg_size)
+        _keep_empty_lines(ld, MODE_CDC, avg_size)
         return write_container(MODE_CDC, avg_size, 0, [], [], [])
     edges = [s for s, _ in bounds] + [n]
     _, method, payloads, st = _lib.encode_blocks_var(bytes(data), edges, candidate_mask(hot_path, v2_new),
                                                      verify=_want_verify(verify), dedup=_want_dedup(dedup),
-                                                     checksums=_want_checksums(checksums))
+                                                     checksums=_want_checksums(checksums), lines=ld)
     _last_stats = st
     _keep_checksums(_want_checksums(checksums), MODE_CDC, avg_size, data, [e - s for s, e in bounds])
+    _keep_lines(ld, MODE_CDC, avg_size, data, [e - s for s, e in bounds])
     return write_container(MODE_CDC, avg_size, n, [int(m) for m in method], [e - s for s, e in bounds], payloads)
 
 
@@ -478,6 +569,16 @@ def _match_toc(cs: Checksums, mode: int, size_field: int, total_len: int, orig) 
                          f"{cs.total_len} bytes; the container: mode {mode}, size field {size_field}, {total_len} bytes)")
     if cs.lens != [int(n) for n in orig]:
         raise ValueError("checksums: the manifest's block lengths differ from the container's")
+
+
+def _match_toc_lines(li: LineIndex, mode: int, size_field: int, total_len: int, orig) -> None:
+    """A line index belongs to a container when mode, size_field, total_len and every block length
+    agree with its TOC."""
+    if (li.mode, li.size_field, li.total_len) != (mode, size_field, total_len):
+        raise ValueError(f"line index: the index is of another container (mode {li.mode}, size field {li.size_field}, "
+                         f"{li.total_len} bytes; the container: mode {mode}, size field {size_field}, {total_len} bytes)")
+    if li.lens != [int(n) for n in orig]:
+        raise ValueError("line index: the index's block lengths differ from the container's")
 
 
 def _host_check(i: int, mid: int, want: int, block: bytes) -> None:
@@ -564,9 +665,16 @@ class Reader:
     `checksums` (a kolm.checksums.Checksums or its sidecar bytes; it must agree with the TOC):
     every read then takes the CRC-32 of the blocks it decodes, on the device where they lie
     (kolm_reader_set_checksums) or with zlib.crc32 for host-decoded blocks, before any byte is
-    handed out: a mismatch raises KolmChecksumError and the read returns nothing."""
+    handed out: a mismatch raises KolmChecksumError and the read returns nothing.
 
-    def __init__(self, container: bytes, ctx=None, checksums=None):
+    `lines` (a kolm.lines.LineIndex or its sidecar bytes, which must agree with the TOC; or True /
+    a one-byte delimiter to build the index at open: every block decoded once, on the device):
+    the record view of the data.  line_count, line_spans, line_of, read_lines and grep then
+    decode only the blocks that hold a delimiter they need (kolm_reader_line_spans /
+    kolm_reader_line_of); an index that does not describe the decoded bytes raises
+    KolmLineIndexError and the call returns nothing."""
+
+    def __init__(self, container: bytes, ctx=None, checksums=None, lines=None):
         blob = bytes(container)
         self._cs = None if checksums is None else as_checksums(checksums)
         self._ctx = ctx
@@ -597,6 +705,35 @@ class Reader:
                 or (m == 10 and (n >= _V2_DEVICE_MAX or _v2_k_above_15(payloads[i]))))]
             if self._host_blocks:
                 self._blob = blob
+        self._li: Optional[LineIndex] = None
+        if lines is not None and lines is not False:
+            try:
+                self._attach_lines(lines, info["orig_lens"])
+            except Exception:
+                self.close()
+                raise
+
+    def _attach_lines(self, lines, orig) -> None:
+        given = isinstance(lines, LineIndex) or (isinstance(lines, (bytes, bytearray, memoryview)) and len(lines) != 1)
+        if given:
+            li = as_line_index(lines)
+            _match_toc_lines(li, self.mode, self.size_field, self._total, orig)
+            _lib.reader_set_lines(self._h, li.delim, li.counts)
+        else:
+            d = 0x0A if lines is True else delim_byte(lines)
+            if self._host_blocks:  # a block the device does not decode: the whole index on the host
+                data = self._read_host([(0, self._total)])[0]
+                li = LineIndex.of_blocks(self.mode, self.size_field, [data[s:s + n] for s, n, _ in self.blocks], d)
+                _lib.reader_set_lines(self._h, d, li.counts)
+            else:
+                li = LineIndex(self.mode, self.size_field, self._total, orig, d,
+                               _lib.reader_index_lines(self._h, d, len(self.blocks)))
+        self._li = li
+
+    @property
+    def line_index(self) -> Optional[LineIndex]:
+        """The attached kolm.lines.LineIndex, or None."""
+        return self._li
 
     def __len__(self) -> int:
         return self._total
@@ -805,6 +942,119 @@ class Reader:
         """The number of matches of every pattern of the set (no emit launch)."""
         return self._search_set(pset, start, end, 0)[2]
 
+    # ---- lines (kolm.lines) ----
+
+    def _lines(self) -> LineIndex:
+        self._handle()
+        if self._li is None:
+            raise ValueError("no line index is attached: open_container(container, lines=True) builds one, "
+                             "lines=<a LineIndex or its sidecar bytes> attaches one")
+        return self._li
+
+    def line_count(self) -> int:
+        """The number of lines: delimiters + 1 (an empty container has one empty line)."""
+        return self._lines().nlines
+
+    def _host_block_positions(self, b: int, cache: Dict[int, List[int]]) -> List[int]:
+        """The delimiter positions of block b through the host decoders (checked against the index)."""
+        if b not in cache:
+            s, n, _ = self.blocks[b]
+            data = self._read_host([(s, n)])[0]
+            cache[b] = [i for i, v in enumerate(data) if v == self._li.delim]
+            if len(cache[b]) != self._li.counts[b]:
+                raise KolmLineIndexError(b, self._li.counts[b], len(cache[b]))
+        return cache[b]
+
+    def _host_lines_stats(self, queries: int, cache) -> None:
+        global _last_lines
+        _last_lines = {"host": True, "queries": queries, "blocks_decoded": len(cache), "groups": 0,
+                       "bytes_decoded": sum(self.blocks[b][1] for b in cache), "ms_decode": 0.0, "ms_lines": 0.0}
+
+    def line_spans(self, lines) -> List[Tuple[int, int]]:
+        """(start, end) of every line number in `lines` (0 .. line_count() - 1; ValueError
+        otherwise, before anything is launched): data[start:end] is the line, without its
+        delimiter.  Only the blocks that hold a bounding delimiter are decoded: the blocks a long
+        line merely passes through are not (kolm_reader_line_spans; last_lines())."""
+        global _last_lines
+        li, h = self._lines(), self._handle()
+        ks = [int(k) for k in lines]
+        D = li.delimiters
+        for i, k in enumerate(ks):
+            if k < 0 or k > D:
+                raise ValueError(f"line {i}: {k} is not one of the container's {D + 1} lines")
+        if self._host_blocks:
+            need = sorted({k - 1 for k in ks if k > 0} | {k for k in ks if k < D})
+            loc = _lib.lines_locate(li.counts, need)
+            if any(b in self._host_blocks for b, _ in loc):
+                cache: Dict[int, List[int]] = {}
+                pos = {k: self._starts[b] + self._host_block_positions(b, cache)[j] for k, (b, j) in zip(need, loc)}
+                self._host_lines_stats(len(need), cache)
+                return [(pos[k - 1] + 1 if k else 0, pos[k] if k < D else self._total) for k in ks]
+        _last_lines = {}
+        return _lib.reader_line_spans(h, ks)
+
+    def line_of(self, offsets) -> List[int]:
+        """The line number of every offset (0 .. len(self)): the delimiters in data[:offset].  A
+        delimiter's own offset belongs to the line it ends.  An offset at a block's start or at the
+        end of the data is answered from the index alone (kolm_reader_line_of)."""
+        global _last_lines
+        li, h = self._lines(), self._handle()
+        offs = [int(o) for o in offsets]
+        for i, o in enumerate(offs):
+            if o < 0 or o > self._total:
+                raise ValueError(f"offset {i}: {o} is not inside the container's {self._total} bytes")
+        if self._host_blocks:
+            loc = _lib.lines_locate_offsets([n for _, n, _ in self.blocks], li.counts, offs)
+            if any(b in self._host_blocks and inb for b, inb, _ in loc):
+                import bisect
+                cache: Dict[int, List[int]] = {}
+                out = [before + (bisect.bisect_left(self._host_block_positions(b, cache), inb) if inb else 0)
+                       for b, inb, before in loc]
+                self._host_lines_stats(sum(1 for _, inb, _ in loc if inb), cache)
+                return out
+        _last_lines = {}
+        return _lib.reader_line_of(h, offs)
+
+    def read_lines(self, first: int, count: int = 1) -> List[bytes]:
+        """Lines first .. first + count - 1 as a list of bytes (no delimiters), clipped at the last
+        line the way read clips at the end of the data: one line_spans call for the two outer
+        lines, then one read of the bytes between them."""
+        li = self._lines()
+        first, count = int(first), int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        if first >= li.nlines or count == 0:
+            return []
+        last = min(first + count, li.nlines) - 1
+        (start, _), (_, end) = self.line_spans([first, last])
+        return self.read_many([(start, end - start)])[0].split(bytes([li.delim]))
+
+    def grep(self, patterns, start: int = 0, end: Optional[int] = None,
+             limit: Optional[int] = None) -> List[Tuple[int, bytes]]:
+        """(line number, line) of the distinct lines that own at least one match of the patterns in
+        data[start:end], ascending; with `limit` the first `limit` lines.  A match belongs to the
+        line its first byte lies in (also when the pattern contains the delimiter).  `patterns`: one
+        bytes-like pattern, a sequence of them (more than 16: a temporary PatternSet) or a
+        PatternSet.  Built from what exists: find_many / find_set, line_of on the match offsets,
+        line_spans, read_many."""
+        self._lines()
+        if limit is not None and int(limit) < 0:
+            raise ValueError("start, end and limit must not be negative")
+        if isinstance(patterns, (bytes, bytearray, memoryview)):
+            patterns = [patterns]
+        if isinstance(patterns, PatternSet) or len(patterns) > _lib.KOLM_FIND_MAX_PATTERNS:
+            hits = self.find_set(patterns, start, end)
+        else:
+            hits = self.find_many(patterns, start, end)
+        offs = sorted({o for o, _ in hits})
+        owners = sorted(set(self.line_of(offs))) if offs else []
+        if limit is not None:
+            owners = owners[:int(limit)]
+        if not owners:
+            return []
+        spans = self.line_spans(owners)
+        return list(zip(owners, self.read_many([(s, e - s) for s, e in spans])))
+
     def read_many_device(self, ranges, dptr: int, cap: int) -> List[int]:
         """The ranges' bytes packed back to back at the device address dptr (cap bytes
         available), left on the device; returns every range's offset in that buffer.  Ranges
@@ -866,6 +1116,16 @@ class PatternSet:
         return self._h
 
 
+def last_lines() -> Dict[str, Any]:
+    """kolm_lines_stats of the last Reader.line_spans / line_of (read_lines and grep end with one):
+    queries, blocks_decoded, groups, bytes_decoded, ms_decode, ms_lines (a call served on the host
+    reports its blocks with groups = 0 and "host": True)."""
+    return dict(_last_lines) if _last_lines.get("host") else _lib.last_lines()
+
+
+_last_lines: Dict[str, Any] = {}
+
+
 def last_find() -> Dict[str, Any]:
     """kolm_find_stats of the last Reader.find / find_many / count / count_many / find_set /
     count_set: patterns,
@@ -885,11 +1145,13 @@ def find(container: bytes, pattern, start: int = 0, end: Optional[int] = None, l
         return r.find(pattern, start, end, limit)
 
 
-def open_container(container: bytes, ctx=None, checksums=None) -> Reader:
+def open_container(container: bytes, ctx=None, checksums=None, lines=None) -> Reader:
     """A Reader over `container` (see Reader).  ctx (optional): a context of kolm._lib.device_ctx
     instead of the default one.  checksums (optional): the container's manifest; reads are then
-    checked.  A malformed container raises what decompress raises."""
-    return Reader(container, ctx, checksums)
+    checked.  lines (optional): the container's line index (a LineIndex or its sidecar bytes), or
+    True / a one-byte delimiter to build one at open.  A malformed container raises what
+    decompress raises."""
+    return Reader(container, ctx, checksums, lines)
 
 
 def verify(container: bytes, data: bytes) -> Dict[str, Any]:

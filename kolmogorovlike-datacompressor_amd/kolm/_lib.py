@@ -21,6 +21,7 @@ import time
 import numpy as np
 
 from .checksums import KolmChecksumError
+from .lines import KolmLineIndexError
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KOLM_LIB") or os.path.join(HERE, "libkolm_hip.so")  # KOLM_LIB: A/B builds
@@ -34,9 +35,11 @@ KOLM_EFORMAT = -6
 KOLM_ERANGE = -7
 KOLM_EVERIFY = -8
 KOLM_ECHECKSUM = -9
+KOLM_ELINES = -10
 ERRORS = {-1: "bad argument", -2: "capacity too small", -3: "HIP error", -4: "collective error",
           -5: "not initialised", -6: "malformed container", -7: "field overflow",
-          -8: "payload does not decode to its input", -9: "decoded bytes do not match their CRC-32"}
+          -8: "payload does not decode to its input", -9: "decoded bytes do not match their CRC-32",
+          -10: "the line index does not describe the decoded bytes"}
 KOLM_VERIFY_EQUAL = 0xFFFFFFFF     # per-block word of the verify entry points: the block is equal
 KOLM_VERIFY_REJECTED = 0xFFFFFFFE  # the decoder rejected the payload
 VR_NONE, VR_DIFFER, VR_REJECTED, VR_LENGTH = 0, 1, 2, 3  # kolm_verify_report.first_bad_reason
@@ -176,6 +179,21 @@ class FindStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LinesStats(ctypes.Structure):
+    _fields_ = [
+        ("queries", ctypes.c_uint32),
+        ("blocks_decoded", ctypes.c_uint32),
+        ("groups", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("bytes_decoded", ctypes.c_uint64),
+        ("ms_decode", ctypes.c_double),
+        ("ms_lines", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class PatsetInfo(ctypes.Structure):
     _fields_ = [
         ("np", ctypes.c_uint32),
@@ -303,6 +321,17 @@ SIGNATURES = [
                                    ctypes.POINTER(ctypes.c_double)]),
     ("kolm_reader_find_set", I32, [P, P, U64, U64, U64, P, ctypes.POINTER(U64), ctypes.POINTER(FindStats)]),
     ("kolm_reader_find_copy32", I32, [P, U64, U64, P, P]),
+    ("kolm_delim_count_device", I32, [P, P, P, U32, U32, P, ctypes.POINTER(ctypes.c_double)]),
+    ("kolm_delim_count_pieces_device", I32, [P, P, P, U32, U32, P, P, U64, ctypes.POINTER(ctypes.c_double)]),
+    ("kolm_lines_locate", I32, [P, U32, P, U32, P, P]),
+    ("kolm_lines_locate_offsets", I32, [P, P, U32, P, U32, P, P, P]),
+    ("kolm_reader_set_lines", I32, [P, U32, P, U32]),
+    ("kolm_reader_index_lines", I32, [P, U32, P, U32, ctypes.POINTER(LinesStats)]),
+    ("kolm_reader_line_spans", I32, [P, P, U32, P, P, ctypes.POINTER(LinesStats)]),
+    ("kolm_reader_line_of", I32, [P, P, U32, P, ctypes.POINTER(LinesStats)]),
+    ("kolm_ctx_set_lines", I32, [P, I32, U32]),
+    ("kolm_set_lines", I32, [I32, U32]),
+    ("kolm_ctx_lines", I32, [P, P, U32, ctypes.POINTER(U32), ctypes.POINTER(U32)]),
 ]
 KOLM_FIND_MAX_PATTERNS = 16
 KOLM_FIND_MAX_LEN = 256
@@ -525,21 +554,69 @@ def last_crcs():
     return None if _last_crcs is None else list(_last_crcs)
 
 
+_last_lines = None
+_ENV_LINES = os.environ.get("KOLM_LINES", "0").strip() not in ("", "0")  # the contexts' own default
+_ENV_LINES_DELIM = int(os.environ.get("KOLM_LINES_DELIM", "10").strip() or "10") & 0xFF
+
+
+def ctx_lines(ctx=None):
+    """(delim, counts) of ctx's (None: the default context's) last encode call, container block
+    order (kolm_ctx_lines): no counts when that call ran with the line index off."""
+    n, d = U32(0), U32(0)
+    check(load().kolm_ctx_lines(ctx, None, 0, ctypes.byref(n), ctypes.byref(d)))
+    cnt = np.zeros(max(n.value, 1), dtype=np.uint32)
+    check(load().kolm_ctx_lines(ctx, cnt.ctypes.data, len(cnt), ctypes.byref(n), ctypes.byref(d)))
+    return int(d.value), [int(c) for c in cnt[:n.value]]
+
+
+class _lines_scope:
+    """Runs one native encode call with the line index on for the delimiter byte `delim`, on ctx
+    (None: the default context), as _checksums_scope does for checksums: the call's counts are
+    kept for last_lines_counts().  The caller holds _result_lock (_encode_scope)."""
+
+    def __init__(self, delim: int, ctx=None):
+        self.delim, self.ctx = delim, ctx
+
+    def _set(self, on: int, delim: int) -> int:
+        L = load()
+        return L.kolm_set_lines(on, delim) if self.ctx is None else L.kolm_ctx_set_lines(self.ctx, on, delim)
+
+    def __enter__(self):
+        check(self._set(1, self.delim))
+        return self
+
+    def __exit__(self, et, ev, tb):
+        global _last_lines
+        if et is None:
+            _last_lines = ctx_lines(self.ctx)
+        self._set(1 if _ENV_LINES else 0, _ENV_LINES_DELIM)
+        return False
+
+
+def last_lines_counts():
+    """(delim, counts) of the last encode call made through this binding, or None when it ran with
+    the line index off (or did not return a result)."""
+    return None if _last_lines is None else (_last_lines[0], list(_last_lines[1]))
+
+
 @contextlib.contextmanager
-def _encode_scope(verify: bool, dedup: bool, locked: bool = False, ctx=None, checksums: bool = False):
+def _encode_scope(verify: bool, dedup: bool, locked: bool = False, ctx=None, checksums: bool = False, lines=None):
     """The switches of one native encode call.  dedup and checksums false: _verify_scope alone,
     the path as it was (last_dedup() then reports nothing, last_crcs() None).  Otherwise
     _result_lock is taken once for all the switches (it is not reentrant), unless the caller holds
     it (locked).  With KOLM_DEDUP / KOLM_CHECKSUMS set in the environment the contexts do it
     whatever the argument says, so the call is treated as if the argument were true and
     last_dedup() / last_crcs() report it."""
-    global _last_dedup, _last_crcs
+    global _last_dedup, _last_crcs, _last_lines
     dedup = bool(dedup) or _ENV_DEDUP
     checksums = bool(checksums) or _ENV_CHECKSUMS
+    if lines is None and _ENV_LINES:  # the contexts count whatever the argument says: report it
+        lines = _ENV_LINES_DELIM
     _last_crcs = None
+    _last_lines = None
     if not dedup:
         _last_dedup = {}
-    if not dedup and not checksums:
+    if not dedup and not checksums and lines is None:
         with _verify_scope(verify, locked, ctx):
             yield
         return
@@ -549,6 +626,8 @@ def _encode_scope(verify: bool, dedup: bool, locked: bool = False, ctx=None, che
         with contextlib.ExitStack() as stack:
             if checksums:
                 stack.enter_context(_checksums_scope(ctx))
+            if lines is not None:
+                stack.enter_context(_lines_scope(int(lines), ctx))
             if dedup:
                 stack.enter_context(_dedup_scope(ctx))
             stack.enter_context(_verify_scope(verify, True, ctx))
@@ -817,7 +896,7 @@ def device_ctx(device: int):
 
 def encode_blocks_device(ctx, d_data: int, n: int, block_size: int, d_arena: int, arena_cap: int,
                          cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False, dedup: bool = False,
-                         checksums: bool = False):
+                         checksums: bool = False, lines=None):
     """Batched MDL encode of fixed blocks of the device buffer d_data[0, n) into the
     device arena (kolm_encode_blocks_device).  Returns (sizes, method, offsets, stats).
     verify: the batch is checked on ctx before the call returns (KolmVerifyError).
@@ -828,7 +907,7 @@ def encode_blocks_device(ctx, d_data: int, n: int, block_size: int, d_arena: int
     method = np.zeros(max(nb, 1), dtype=np.uint32)
     off = np.zeros(nb + 1, dtype=np.uint64)
     st = Stats()
-    with _encode_scope(verify, dedup, ctx=ctx, checksums=checksums):
+    with _encode_scope(verify, dedup, ctx=ctx, checksums=checksums, lines=lines):
         check(load().kolm_encode_blocks_device(ctx, d_data, n, block_size, cand_mask, None, d_arena, arena_cap,
                                                sizes.ctypes.data, method.ctypes.data, off.ctypes.data,
                                                ctypes.byref(st)), ctx)
@@ -962,7 +1041,7 @@ def bbwt_mtf_rice(data: bytes, flags: int, k: int = 2) -> bytes:
 
 
 def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, force=None,
-                  verify: bool = False, dedup: bool = False, checksums: bool = False):
+                  verify: bool = False, dedup: bool = False, checksums: bool = False, lines=None):
     """Batched MDL encode of fixed-size blocks.  Returns (sizes[nb,KOLM_NCAND], method[nb],
     payloads list, stats dict).  verify: check the payloads on the device before returning
     (KolmVerifyError on a bad block).  dedup: repeated blocks are encoded once.  checksums:
@@ -985,7 +1064,7 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MA
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    with _encode_scope(verify, dedup, checksums=checksums):
+    with _encode_scope(verify, dedup, checksums=checksums, lines=lines):
         check(load().kolm_encode_blocks(
             data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
             fz.ctypes.data if fz is not None else None,
@@ -996,7 +1075,7 @@ def encode_blocks(data: bytes, block_size: int, cand_mask: int = KOLM_DEFAULT_MA
 
 
 def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, verify: bool = False,
-                   dedup: bool = False, checksums: bool = False):
+                   dedup: bool = False, checksums: bool = False, lines=None):
     """The whole KOLR container of data in fixed blocks (kolm_compress_fixed): (bytes, stats).
     verify: every device batch is checked before its payloads count (KolmVerifyError, no
     container, on a bad block).  dedup: every device batch encodes its repeated blocks once.
@@ -1011,7 +1090,7 @@ def compress_fixed(data, block_size: int, cand_mask: int = KOLM_DEFAULT_MASK, ve
     # copy out of it run under one lock (ctypes drops the GIL inside the call)
     with _result_lock:
         tc = time.perf_counter() if _HOST_PROF else 0.0
-        with _encode_scope(verify, dedup, locked=True, checksums=checksums):
+        with _encode_scope(verify, dedup, locked=True, checksums=checksums, lines=lines):
             rc = load().kolm_compress_fixed(src.ctypes.data, n, block_size, cand_mask, ctypes.byref(out),
                                             ctypes.byref(ln), ctypes.byref(st))
             if rc == KOLM_EVERIFY:
@@ -1049,7 +1128,7 @@ def _new_bytes(n: int) -> bytes:
 
 
 def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, force=None, verify: bool = False,
-                      dedup: bool = False, checksums: bool = False):
+                      dedup: bool = False, checksums: bool = False, lines=None):
     """Batched MDL encode of content-defined blocks: block i = data[bounds[i]:bounds[i+1]]
     (bounds[0] = 0, strictly increasing, bounds[-1] = len(data)).  Same return value as
     encode_blocks."""
@@ -1072,7 +1151,7 @@ def encode_blocks_var(data: bytes, bounds, cand_mask: int = KOLM_DEFAULT_MASK, f
         if fz.shape != (nb,):
             raise ValueError("force must have one entry per block")
     st = Stats()
-    with _encode_scope(verify, dedup, checksums=checksums):
+    with _encode_scope(verify, dedup, checksums=checksums, lines=lines):
         check(load().kolm_encode_blocks(
             data, starts.ctypes.data, lens.ctypes.data, nb, cand_mask,
             fz.ctypes.data if fz is not None else None,
@@ -1429,3 +1508,138 @@ def reader_read_device(h, ranges, dptr: int, cap: int):
     _read_check(load().kolm_reader_read_device(h, offs.ctypes.data, lens.ctypes.data, len(ranges), dptr, cap,
                                                ctypes.byref(st)))
     _last_read = st.as_dict()
+
+
+# ---- line index (kolm_delim_count_device, kolm_reader_line_*) ------------------------------
+
+_last_lines_stats: dict = {}
+_LINES_MSG = re.compile(r"block (\d+): expected (\d+) delimiters, got (\d+)")
+
+
+def last_lines() -> dict:
+    """kolm_lines_stats of the last line call made through this binding."""
+    return dict(_last_lines_stats)
+
+
+def delim_count_device(ctx, d_data: int, bounds, delim: int):
+    """kolm_delim_count_device: (the blocks' delimiter counts as a list, k_delim_count's device ms)."""
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
+    nb = len(b) - 1
+    cnt = np.zeros(max(nb, 1), dtype=np.uint32)
+    ms = ctypes.c_double(0.0)
+    check(load().kolm_delim_count_device(ctx, d_data, b.ctypes.data, nb, delim, cnt.ctypes.data, ctypes.byref(ms)))
+    return [int(c) for c in cnt[:nb]], ms.value
+
+
+def delim_count_pieces_device(ctx, d_data: int, bounds, delim: int):
+    """kolm_delim_count_pieces_device: (the blocks' counts, their 4 KiB pieces' counts block after
+    block, device ms of k_delim_count and the scan of the piece counts)."""
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
+    nb = len(b) - 1
+    npc = int(((np.diff(b) + np.uint64(4095)) // np.uint64(4096)).sum()) if nb else 0
+    cnt, pc = np.zeros(max(nb, 1), dtype=np.uint32), np.zeros(max(npc, 1), dtype=np.uint32)
+    ms = ctypes.c_double(0.0)
+    check(load().kolm_delim_count_pieces_device(ctx, d_data, b.ctypes.data, nb, delim, cnt.ctypes.data, pc.ctypes.data, npc,
+                                                ctypes.byref(ms)))
+    return [int(c) for c in cnt[:nb]], [int(c) for c in pc[:npc]], ms.value
+
+
+def delim_counts(data, delim: int, block_size=None, bounds=None, device: int = None, data_offset: int = 0):
+    """Uploads data and returns its blocks' counts of the byte `delim` (delim_count_device).  bounds
+    may hold empty blocks (equal neighbours): their count is 0."""
+    n = len(data)
+    if bounds is None:
+        if n == 0:
+            return []
+        b = _bounds_array(n, block_size, None)
+    else:
+        bl = [int(x) for x in bounds]
+        if not bl or bl[0] != 0 or bl[-1] != n or any(y < x for x, y in zip(bl, bl[1:])):
+            raise ValueError("bounds must start at 0, not decrease and end at len(data)")
+        b = np.ascontiguousarray(np.asarray(bl, dtype=np.uint64))
+    return _on_device(data, data_offset, device, lambda ctx, p: delim_count_device(ctx, p, b, delim))[0]
+
+
+def lines_locate(counts, idx):
+    """kolm_lines_locate (host only): [(block, number inside the block)] of the delimiter numbers
+    idx; ValueError for a number at or above the sum of counts."""
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32))
+    i = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64))
+    blk, j = np.zeros(max(len(i), 1), dtype=np.uint32), np.zeros(max(len(i), 1), dtype=np.uint32)
+    rc = load().kolm_lines_locate(c.ctypes.data, len(c), i.ctypes.data, len(i), blk.ctypes.data, j.ctypes.data)
+    if rc == -1:
+        raise ValueError(load().kolm_last_error().decode())
+    check(rc)
+    return [(int(a), int(b)) for a, b in zip(blk[:len(i)], j[:len(i)])]
+
+
+def lines_locate_offsets(orig_lens, counts, offs):
+    """kolm_lines_locate_offsets (host only): [(block, offset inside it, delimiters before the
+    block)] of the stream offsets offs; ValueError for an offset above the sum of orig_lens."""
+    ln = np.ascontiguousarray(np.asarray(orig_lens, dtype=np.uint32))
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32))
+    o = np.ascontiguousarray(np.asarray(offs, dtype=np.uint64))
+    m = max(len(o), 1)
+    blk, inb, bef = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint64)
+    rc = load().kolm_lines_locate_offsets(ln.ctypes.data, c.ctypes.data, len(c), o.ctypes.data, len(o), blk.ctypes.data,
+                                          inb.ctypes.data, bef.ctypes.data)
+    if rc == -1:
+        raise ValueError(load().kolm_last_error().decode())
+    check(rc)
+    return [(int(a), int(b), int(d)) for a, b, d in zip(blk[:len(o)], inb[:len(o)], bef[:len(o)])]
+
+
+def _lines_check(rc):
+    if rc == KOLM_ELINES:  # the message names the block (kolm.h)
+        m = _LINES_MSG.search(load().kolm_last_error().decode())
+        if m:
+            raise KolmLineIndexError(int(m.group(1)), int(m.group(2)), int(m.group(3)))
+        raise KolmLineIndexError(-1, 0, 0)  # a text this binding does not know: still the line index error
+    _read_check(rc)
+
+
+def reader_set_lines(h, delim: int, counts):
+    """kolm_reader_set_lines: the delimiter count of every block (None detaches)."""
+    if counts is None:
+        check(load().kolm_reader_set_lines(h, 0, None, 0))
+        return
+    c = np.ascontiguousarray(np.asarray(list(counts) or [0], dtype=np.uint32))
+    rc = load().kolm_reader_set_lines(h, delim, c.ctypes.data, len(counts))
+    if rc == -1:
+        raise ValueError(load().kolm_last_error().decode())
+    check(rc)
+
+
+def reader_index_lines(h, delim: int, nblocks: int):
+    """kolm_reader_index_lines: builds and attaches the index; returns the counts."""
+    global _last_lines_stats
+    cnt = np.zeros(max(nblocks, 1), dtype=np.uint32)
+    st = LinesStats()
+    _lines_check(load().kolm_reader_index_lines(h, delim, cnt.ctypes.data, max(nblocks, 1), ctypes.byref(st)))
+    _last_lines_stats = st.as_dict()
+    return [int(c) for c in cnt[:nblocks]]
+
+
+def reader_line_spans(h, lines):
+    """kolm_reader_line_spans: [(start, end)] of the lines.  ValueError for what the library
+    refuses, KolmChecksumError / KolmLineIndexError as it reports them; last_lines() then keeps
+    what it held."""
+    global _last_lines_stats
+    k = np.ascontiguousarray(np.asarray(lines, dtype=np.uint64))
+    m = max(len(k), 1)
+    a, b = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)
+    st = LinesStats()
+    _lines_check(load().kolm_reader_line_spans(h, k.ctypes.data, len(k), a.ctypes.data, b.ctypes.data, ctypes.byref(st)))
+    _last_lines_stats = st.as_dict()
+    return [(int(x), int(y)) for x, y in zip(a[:len(k)], b[:len(k)])]
+
+
+def reader_line_of(h, offsets):
+    """kolm_reader_line_of: the line number of every offset (errors as reader_line_spans)."""
+    global _last_lines_stats
+    o = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+    out = np.zeros(max(len(o), 1), dtype=np.uint64)
+    st = LinesStats()
+    _lines_check(load().kolm_reader_line_of(h, o.ctypes.data, len(o), out.ctypes.data, ctypes.byref(st)))
+    _last_lines_stats = st.as_dict()
+    return [int(x) for x in out[:len(o)]]

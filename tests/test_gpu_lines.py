@@ -1,0 +1,415 @@
+"""The line index on the device (kolmogorovlike-datacompressor_amd/csrc/k_lines.hip, kolm_api.cpp):
+k_delim_count against bytes.count and the CPU emulation (tools/lines_emu.cpp), and a Reader's
+line_count / line_spans / line_of / read_lines / grep over containers made here against
+data.split, a host list of the delimiter positions with bisect, and repeated bytes.find.  No
+expected value comes from the code under test."""
+import bisect
+import ctypes
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden")
+DELIMS = (0x0A, 0x00, 0xFF)
+LENS = (0, 1, 15, 16, 17, 4095, 4096, 4097, 8193, 32768, 32773)  # the last two straddle the 8-piece run
+KINDS = ("all", "none", "word_edges", "piece_edges", "mix")
+BLOCK_SIZES = (1000, 4096, 4097, 8193)
+GEOMS = tuple(f"fixed{bs}" for bs in BLOCK_SIZES) + ("cdc",)
+SHAPES = ("short", "long", "runs", "block_edges", "ends_delim", "only", "none", "empty")
+N = 40_000
+
+
+def fill(kind, n, d):
+    other = d ^ 0x5A
+    i = np.arange(n, dtype=np.uint64)
+    if kind == "all":
+        hit = np.ones(n, bool)
+    elif kind == "none":
+        hit = np.zeros(n, bool)
+    elif kind == "word_edges":
+        hit = ((i & 15) == 15) | ((i & 15) == 0)
+    elif kind == "piece_edges":
+        hit = ((i & 4095) == 4095) | ((i & 4095) == 0)
+    else:
+        hit = np.random.default_rng(n * 7 + d).integers(0, 2, n).astype(bool)
+    return np.where(hit, d, other).astype(np.uint8).tobytes()
+
+
+@pytest.fixture(scope="module")
+def lib(kolm_gpu):
+    from kolm import _lib
+    return _lib
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("lin") / "lines_emu.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", os.path.join(REPO, "tools", "lines_emu.cpp"), "-o", so],
+                   check=True)
+    lib = ctypes.CDLL(so)
+    P, U32, U64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
+    lib.lines_emu_count.argtypes = [P, U64, P, U32, U32, U32, U32, P, P]
+    lib.lines_emu_count.restype = U64
+    return lib
+
+
+def emu_counts(emu, batch, bounds, d, lead):
+    raw = np.full(len(batch) + 64, d, np.uint8)
+    at = 16 + (lead - (raw.ctypes.data + 16)) % 16
+    raw[at:at + len(batch)] = np.frombuffer(batch, np.uint8)
+    b = np.ascontiguousarray(np.asarray(bounds, np.uint64))
+    out = np.full(len(b) - 1, 0xDEADBEEF, np.uint32)
+    bad = emu.lines_emu_count(raw.ctypes.data + at, len(batch), b.ctypes.data, len(b) - 1, d, 0, 0, out.ctypes.data, None)
+    assert bad == 0
+    return [int(x) for x in out]
+
+
+# ------------------------------------------------------------------ 1. kolm_delim_count_device
+
+@pytest.mark.parametrize("d", DELIMS)
+def test_delim_count_device(kolm_gpu, lib, emu, d):
+    """Every length and data kind as a block of one batch whose other blocks are the delimiter
+    itself (a count that leaks past a block's end shows), at every data_offset."""
+    db = bytes([d])
+    blocks = []
+    for n in LENS:
+        for kind in KINDS:
+            blocks += [fill(kind, n, d), db * 5]
+    batch = b"".join(blocks)
+    bounds = np.concatenate(([0], np.cumsum([len(b) for b in blocks]))).tolist()
+    want = [b.count(db) for b in blocks]
+    for off in range(16):
+        assert lib.delim_counts(batch, d, bounds=bounds, data_offset=off) == want, off
+    for off in (0, 7, 15):
+        assert emu_counts(emu, batch, bounds, d, off) == want, off
+    want_pieces = [b[k:k + 4096].count(db) for b in blocks for k in range(0, len(b), 4096)]
+    for off in (0, 3, 8, 15):  # the pass of the line queries: the 4 KiB pieces' counts as well
+        got = lib._on_device(batch, off, None, lambda ctx, p: lib.delim_count_pieces_device(ctx, p, bounds, d))
+        assert got[0] == want and got[1] == want_pieces, off
+    # one block alone: both ends of the batch are the block's
+    for n in (1, 17, 4097):
+        for off in range(16):
+            blk = fill("mix", n, d)
+            assert lib.delim_counts(blk, d, bounds=[0, n], data_offset=off) == [blk.count(db)], (n, off)
+
+
+# ------------------------------------------------------------------ 2. readers over containers made here
+
+def make_data(shape):
+    if shape == "empty":
+        return b""
+    if shape == "only":
+        return b"\n" * N
+    if shape == "none":
+        return (b"no newline in here at all, only words and spaces; " * (N // 50 + 1))[:N]
+    if shape == "short":
+        out = b"".join(b"line %d: %s\n" % (i, b"word " * (i % 9)) for i in range(4000))[:N]
+        return out[:-1] + b"x" if out.endswith(b"\n") else out  # does not end with a delimiter
+    if shape == "ends_delim":
+        return b"".join(b"%d,%d,field\n" % (i, i * i) for i in range(5000))[:N - 1].rsplit(b"\n", 1)[0] + b"\n"
+    if shape == "long":  # a line longer than three blocks of every geometry, short lines around it
+        return b"head\n" + b"y" * 30_000 + b"\n" + b"".join(b"tail %d\n" % i for i in range(2000))[:N - 30_006]
+    if shape == "runs":
+        return b"".join(b"a%d" % i + b"\n" * (1 + i % 7) for i in range(9000))[:N]
+    a = bytearray(b"z" * N)  # block_edges: a delimiter as the first and as the last byte of a block
+    for bs in BLOCK_SIZES:
+        for k in range(bs, N, bs):
+            a[k] = a[k - 1] = 0x0A
+    a[0] = 0x0A
+    return bytes(a)
+
+
+@pytest.fixture(scope="module")
+def cases(kolm_gpu):
+    """(shape, geometry) -> (container, data), made on first use with the hot-path mask."""
+    kolm, made = kolm_gpu, {}
+
+    def get(shape, geom):
+        if (shape, geom) not in made:
+            data = make_data(shape)
+            if geom == "cdc":
+                blob = kolm.compress_blocks_cdc(data, 1024, 2048, 4096, hot_path=True)
+            else:
+                blob = kolm.compress_blocks_fixed(data, int(geom[5:]), hot_path=True)
+            made[(shape, geom)] = (blob, data)
+        return made[(shape, geom)]
+    return get
+
+
+def find_all(data, pats, lo=0, hi=None):
+    hi = len(data) if hi is None else hi
+    d, out = data[lo:hi], set()
+    for p in pats:
+        o = d.find(p)
+        while o >= 0:
+            out.add(lo + o)
+            o = d.find(p, o + 1)
+    return sorted(out)
+
+
+class Ref:
+    """The host's view: delimiter positions, lines by split, line_of by bisect, grep by find."""
+
+    def __init__(self, data, d=0x0A):
+        self.data, self.db = data, bytes([d])
+        self.pos = [i for i, v in enumerate(data) if v == d]
+        self.lines = data.split(self.db)
+        assert len(self.lines) == data.count(self.db) + 1 == len(self.pos) + 1
+        self.spans = [((self.pos[k - 1] + 1) if k else 0, self.pos[k] if k < len(self.pos) else len(data))
+                      for k in range(len(self.lines))]
+        assert all(data[s:e] == ln for (s, e), ln in zip(self.spans[:50] + self.spans[-50:], self.lines[:50] + self.lines[-50:]))
+
+    def line_of(self, o):
+        return bisect.bisect_left(self.pos, o)
+
+    def grep(self, pats, lo=0, hi=None, limit=None):
+        owners = sorted({self.line_of(o) for o in find_all(self.data, pats, lo, hi)})
+        return [(k, self.lines[k]) for k in (owners if limit is None else owners[:limit])]
+
+
+def sample_lines(nl):
+    ks = set(range(min(nl, 40))) | set(range(max(0, nl - 40), nl)) | {nl // 2, nl // 3}
+    ks |= {int(x) for x in np.random.default_rng(nl).integers(0, nl, 60)}
+    ks = sorted(k for k in ks if 0 <= k < nl)
+    return ks + ks[::-1][:5] + ks[:3]  # unsorted, with repeats
+
+
+def check_reader(kolm, rd, ref):
+    data, nl, total = ref.data, len(ref.lines), len(ref.data)
+    assert rd.line_count() == nl
+    ks = sample_lines(nl)
+    assert rd.line_spans(ks) == [ref.spans[k] for k in ks]
+    assert rd.line_spans([]) == []
+    offs = list(range(min(4097, total))) + [total]
+    assert rd.line_of(offs) == [ref.line_of(o) for o in offs]
+    far = sorted({int(x) for x in np.random.default_rng(total + 1).integers(0, total + 1, 40)})
+    assert rd.line_of(far[::-1]) == [ref.line_of(o) for o in far[::-1]]
+    for first, count in ((0, 1), (0, 3), (nl // 2, 25), (nl - 1, 1), (nl - 2, 10), (nl, 4), (5, 0)):
+        if first >= 0:
+            assert rd.read_lines(first, count) == ref.lines[first:first + count], (first, count)
+    # grep: one pattern, 16 patterns (in a window), a PatternSet, a pattern that holds the delimiter, a limit
+    mid = total // 2
+    one = data[mid:mid + 4] or b"zz"
+    assert rd.grep(one) == ref.grep([one])
+    assert rd.grep([one], limit=3) == ref.grep([one], limit=3)
+    lo, hi = total // 3, min(total, total // 3 + 6000)
+    pats16 = [data[k:k + 2 + k % 5] or b"q" for k in range(lo + 7, lo + 7 + 16 * 131, 131)]
+    assert len(pats16) == 16
+    assert rd.grep(pats16, lo, hi) == ref.grep(pats16, lo, hi)
+    assert rd.grep(pats16, lo, hi, limit=2) == ref.grep(pats16, lo, hi, limit=2)
+    with kolm.PatternSet(sorted(set(pats16))) as ps:
+        assert rd.grep(ps, lo, hi) == ref.grep(pats16, lo, hi)
+    p = ref.pos[len(ref.pos) // 2] if ref.pos else 0
+    across = data[p - 2:p + 3] if ref.pos and 2 <= p <= total - 3 else b"ab\ncd"
+    assert rd.grep(across) == ref.grep([across])
+    if ref.pos and 2 <= p <= total - 3:
+        assert (ref.line_of(p - 2), ref.lines[ref.line_of(p - 2)]) in rd.grep(across)  # the line of its first byte
+
+
+@pytest.mark.parametrize("geom", GEOMS)
+@pytest.mark.parametrize("shape", SHAPES)
+def test_reader_lines(kolm_gpu, cases, monkeypatch, shape, geom):
+    kolm = kolm_gpu
+    blob, data = cases(shape, geom)
+    ref = Ref(data)
+    for limit in (None, "8192"):  # one group, many groups: equal results
+        monkeypatch.delenv("KOLM_READ_BYTES", raising=False)
+        if limit:
+            monkeypatch.setenv("KOLM_READ_BYTES", limit)
+        with kolm.open_container(blob, lines=True) as rd:
+            assert rd.line_index.counts == [data[s:s + n].count(b"\n") for s, n, _ in rd.blocks]
+            check_reader(kolm, rd, ref)
+            if limit and len(data) > 3 * 8192:  # an offset inside every block: more bytes than one group holds
+                offs = [s + 1 for s, n, _ in rd.blocks if n > 1]
+                assert rd.line_of(offs) == [ref.line_of(o) for o in offs]
+                assert kolm.last_lines()["groups"] >= 2 and kolm.last_lines()["blocks_decoded"] == len(offs)
+
+
+@pytest.mark.parametrize("geom", GEOMS)
+def test_long_line_decodes_two_blocks(kolm_gpu, cases, geom):
+    """The blocks a long line merely passes through are never touched."""
+    kolm = kolm_gpu
+    blob, data = cases("long", geom)
+    with kolm.open_container(blob, lines=True) as rd:
+        assert rd.line_spans([1]) == [(5, 30_005)] and data[5:30_005] == b"y" * 30_000
+        st = kolm.last_lines()
+        first = bisect.bisect_right(rd._starts, 4) - 1
+        last = bisect.bisect_right(rd._starts, 30_005) - 1
+        assert last - first >= 3 and st["blocks_decoded"] == 2 and st["queries"] == 2
+        assert st["bytes_decoded"] == rd.blocks[first][1] + rd.blocks[last][1]
+        # an offset at a block's start and the end of the data need no decode
+        assert rd.line_of([rd._starts[2], len(data)]) == [data[:rd._starts[2]].count(b"\n"), data.count(b"\n")]
+        assert kolm.last_lines()["blocks_decoded"] == 0
+
+
+# ------------------------------------------------------------------ 3. the index, however it is made
+
+@pytest.mark.parametrize("delim", (b"\n", b"\0"))
+def test_index_four_ways(kolm_gpu, delim):
+    from kolm.lines import LineIndex
+    kolm = kolm_gpu
+    rng = np.random.default_rng(3)
+    data = bytes(rng.choice(np.frombuffer(b"ab \n\0", np.uint8), 30_011))
+    for bs in (1000, 4097):  # block lengths that are no multiple of 16
+        blocks = [data[i:i + bs] for i in range(0, len(data), bs)]
+        want = LineIndex.of_blocks(kolm.MODE_FIXED, bs, blocks, delim)
+        assert want.counts == [b.count(delim) for b in blocks]
+        plain = kolm.compress_blocks_fixed(data, bs, hot_path=True)
+        assert kolm.last_line_index() is None
+        blob = kolm.compress_blocks_fixed(data, bs, hot_path=True, lines=delim if delim != b"\n" else True)
+        assert blob == plain  # the switch does not change the container
+        assert kolm.last_line_index() == want
+        assert kolm.line_index(data, bs, delim=delim) == want
+        assert kolm.line_index_of(blob, delim) == want
+        assert LineIndex.from_bytes(want.to_bytes()) == want
+    edges = kolm.cdc_fast_boundaries_strict(data, 1024, 2048, 4096)
+    want = LineIndex.of_blocks(kolm.MODE_CDC, 2048, [data[s:e] for s, e in edges], delim)
+    plain = kolm.compress_blocks_cdc(data, 1024, 2048, 4096, hot_path=True)
+    assert kolm.compress_blocks_cdc(data, 1024, 2048, 4096, hot_path=True, lines=delim) == plain
+    assert kolm.last_line_index() == want == kolm.line_index_of(plain, delim)
+    assert kolm.line_index(data, bounds=[0] + [e for _, e in edges], delim=delim, size_field=2048) == want
+    kolm.encode_blocks(data, 4097, hot_path=True, lines=delim)
+    assert kolm.last_line_index().counts == [data[i:i + 4097].count(delim) for i in range(0, len(data), 4097)]
+    assert kolm.compress_blocks_fixed(b"", 4096, lines=True) == kolm.compress_blocks_fixed(b"", 4096)
+    with kolm.open_container(plain, lines=delim) as rd:  # another delimiter than the default, end to end
+        ref = Ref(data, delim[0])
+        assert rd.line_count() == len(ref.lines)
+        ks = sample_lines(len(ref.lines))
+        assert rd.line_spans(ks) == [ref.spans[k] for k in ks]
+        assert rd.read_lines(7, 30) == ref.lines[7:37]
+
+
+# ------------------------------------------------------------------ 4. what must be refused
+
+def test_stale_index(kolm_gpu, cases):
+    from kolm.lines import KolmLineIndexError, LineIndex
+    kolm = kolm_gpu
+    blob, data = cases("short", "fixed4096")
+    good = kolm.line_index_of(blob)
+    ref = Ref(data)
+    for b, delta in ((3, 1), (3, -1), (0, -1)):
+        counts = list(good.counts)
+        counts[b] += delta
+        stale = LineIndex(good.mode, good.size_field, good.total_len, good.lens, good.delim, counts)
+        with kolm.open_container(blob, lines=stale.to_bytes()) as rd:
+            assert rd.line_count() == len(ref.lines) + delta  # the index is believed until a block disagrees
+            k = sum(counts[:b])  # the first line that ends in block b
+            with pytest.raises(KolmLineIndexError) as ei:
+                rd.line_spans([k])
+            assert (ei.value.block, ei.value.expected, ei.value.got) == (b, counts[b], good.counts[b])
+            with pytest.raises(KolmLineIndexError) as ei:
+                rd.line_of([b * 4096 + 100])
+            assert ei.value.block == b
+            with pytest.raises(KolmLineIndexError):
+                rd.read_lines(k, 2)
+            if b:  # a block in front of the stale one still answers
+                assert rd.line_spans([1]) == [ref.spans[1]]
+
+
+def test_index_of_another_geometry(kolm_gpu, cases):
+    kolm = kolm_gpu
+    blob, _ = cases("short", "fixed1000")
+    other = kolm.line_index_of(cases("short", "fixed4096")[0])
+    with pytest.raises(ValueError, match="line index"):
+        kolm.open_container(blob, lines=other)
+    with pytest.raises(ValueError, match="line index"):
+        kolm.open_container(blob, lines=other.to_bytes())
+    with kolm.open_container(blob) as rd:
+        assert rd.line_index is None
+        for call in (rd.line_count, lambda: rd.line_spans([0]), lambda: rd.line_of([0]), lambda: rd.read_lines(0),
+                     lambda: rd.grep(b"a")):
+            with pytest.raises(ValueError, match="lines="):
+                call()
+    with kolm.open_container(blob, lines=True) as rd:
+        n = rd.line_count()
+        for call in (lambda: rd.line_spans([n]), lambda: rd.line_spans([-1]), lambda: rd.line_of([len(rd) + 1]),
+                     lambda: rd.read_lines(-1)):
+            with pytest.raises(ValueError):
+                call()
+
+
+def test_library_argument_errors(kolm_gpu, lib, cases):
+    """The library's own checks, behind the binding's: the message names the entry."""
+    kolm = kolm_gpu
+    blob, data = cases("short", "fixed4096")
+    with kolm.open_container(blob, lines=True) as rd:
+        n = rd.line_count()
+        with pytest.raises(ValueError, match="entry 1: line"):
+            lib.reader_line_spans(rd._h, [0, n])
+        with pytest.raises(ValueError, match="entry 2: offset"):
+            lib.reader_line_of(rd._h, [0, 1, len(data) + 1])
+        with pytest.raises(ValueError, match="block count"):
+            lib.reader_set_lines(rd._h, 10, [1, 2, 3])
+    with kolm.open_container(blob) as rd:
+        with pytest.raises(ValueError, match="no line index"):
+            lib.reader_line_spans(rd._h, [0])
+
+
+def test_checksums_guard_line_calls(kolm_gpu):
+    """One payload byte of a raw block flipped: a line call that selects the block raises and
+    returns nothing; the calls that do not select it still answer."""
+    from kolm.checksums import KolmChecksumError
+    kolm = kolm_gpu
+    noise = bytes(np.random.default_rng(9).integers(0, 256, 4096, dtype=np.uint8))
+    text = b"".join(b"row %d\n" % i for i in range(3000))[:3 * 4096]
+    data = text + noise + text
+    blob = kolm.compress_blocks_fixed(data, 4096, hot_path=True)
+    cs, li = kolm.checksums_of(blob), kolm.line_index_of(blob)
+    _, _, _, mids, _, off, start = kolm.read_toc(blob)
+    assert int(mids[3]) == 0  # the noise block is stored raw: a flipped byte decodes, to other bytes
+    at = next(i for i in range(100, 4096) if noise[i] != 0x0A and noise[i] ^ 0x01 != 0x0A)
+    bad = bytearray(blob)
+    bad[start + int(off[3]) + at] ^= 0x01
+    ref = Ref(data)
+    with kolm.open_container(bytes(bad), checksums=cs, lines=li) as rd:
+        k = ref.line_of(4 * 4096)  # the line that ends with the first delimiter behind block 3 begins in it
+        assert 3 * 4096 <= ref.spans[k][0] < 4 * 4096
+        for call in (lambda: rd.line_spans([k]), lambda: rd.line_of([3 * 4096 + at]), lambda: rd.read_lines(k),
+                     lambda: rd.grep(noise[at:at + 6])):
+            with pytest.raises(KolmChecksumError) as ei:
+                call()
+            assert ei.value.block == 3
+        assert rd.line_spans([1, 2]) == ref.spans[1:3] and rd.line_of([5000]) == [ref.line_of(5000)]
+
+
+def test_host_decoded_block_gives_the_same(kolm_gpu, lib, monkeypatch):
+    kolm = kolm_gpu
+    z = np.load(os.path.join(GOLDEN, "v2new.npz"))
+    with open(os.path.join(GOLDEN, "v2new.json")) as f:
+        names = list(json.load(f)["containers"])
+    for c in names:
+        blob, data = z[f"C/{c}/full10"].tobytes(), z[f"C/{c}/input"].tobytes()
+        mids = kolm.read_container(blob)[3]
+        if 10 in mids and any(m != 10 for m in mids):
+            break
+    else:
+        pytest.fail("no golden container mixes id 10 with other ids")
+    d = max(set(data), key=data.count)  # a delimiter the data holds
+    ref = Ref(data, d)
+    ks = sample_lines(len(ref.lines))
+    offs = list(range(0, len(data) + 1, 37)) + [len(data)]
+    pat = data[len(data) // 2:len(data) // 2 + 3]
+
+    def run(rd):
+        return (rd.line_count(), rd.line_spans(ks), rd.line_of(offs), rd.read_lines(1, 9), rd.grep(pat, limit=7),
+                rd.line_index)
+    with kolm.open_container(blob, lines=bytes([d])) as rd:
+        dev = run(rd)
+        assert "host" not in kolm.last_lines()
+    monkeypatch.setattr(lib, "KOLM_DECODE_MASK", lib.KOLM_DECODE_MASK & ~(1 << 10))
+    with kolm.open_container(blob, lines=bytes([d])) as rd:
+        assert rd._host_blocks
+        host = run(rd)
+        hb = next(b for b in rd._host_blocks if rd.line_index.counts[b])
+        k = sum(rd.line_index.counts[:hb])  # the line that ends with the host-decoded block's first delimiter
+        assert rd.line_spans([k]) == [ref.spans[k]] and kolm.last_lines().get("host") is True
+        assert rd.line_of([ref.pos[k] + 1]) == [k + 1] and kolm.last_lines().get("host") is True
+    assert dev == host
+    assert dev[:5] == (len(ref.lines), [ref.spans[k] for k in ks], [ref.line_of(o) for o in offs], ref.lines[1:10],
+                       ref.grep([pat], limit=7))
