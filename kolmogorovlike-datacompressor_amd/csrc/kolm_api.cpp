@@ -6,456 +6,28 @@
 //   MDL argmin -> payload emission
 // entirely on the device; the host only reads small per-round counters (to size the
 // next launches) and the per-block results.  See DESIGN.md §2-§6.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <atomic>
+//
+// This file: the context, encode, decode, verify, dedup and the context-level checksum and
+// line-count calls.  struct kolm_ctx itself is in kolm_ctx.h.  Readers, searches and pattern sets
+// (random-access reads, find, find_set, the line index of a container) have their own source file:
+// DESIGN.md §1, rows g, j, k and l, name it and what it holds.
 #include <chrono>
-#include <sys/mman.h>  // madvise (kolm_result_copy)
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
+#include <sys/mman.h>  // madvise (kolm_result_copy)
 
-#include "../../include/kolm.h"
-#include "kolm_internal.h"
+#include "kolm_ctx.h"
 #include "verify_core.h"
 #include "dedup_core.h"
 #include "crc_core.h"
 
-using namespace kolm;
-
 namespace kolm {
 thread_local std::string g_err;  // kolm_last_error(); also set by kolm_toc.cpp
 void set_err(const std::string& s) { g_err = s; }
-}  // namespace kolm
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-// Host-side copy workers for the pinned staging buffers: a host buffer of the caller
-// (pageable) is copied into pinned memory by several threads at once, so the DMA engine
-// sees pinned memory and the host side keeps up with PCIe (one thread's memcpy does not).
-class CopyPool {
-  public:
-    explicit CopyPool(unsigned n) {
-        for (unsigned i = 0; i < n; ++i) th_.emplace_back([this] { loop(); });
-    }
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    // dst[0, n) = src[0, n), split over the workers and the calling thread
-    void copy(void* dst, const void* src, size_t n) {
-        const size_t parts = th_.size() + 1, piece = ((n + parts - 1) / parts + 4095) & ~(size_t)4095;
-        std::vector<Job> jobs;
-        for (size_t o = piece; o < n; o += piece)
-            jobs.push_back({(char*)dst + o, (const char*)src + o, std::min(piece, n - o)});
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            for (auto& j : jobs) q_.push_back(j);
-            pending_ += jobs.size();
-        }
-        cv_.notify_all();
-        std::memcpy(dst, src, std::min(piece, n));
-        std::unique_lock<std::mutex> g(mu_);
-        done_cv_.wait(g, [this] { return pending_ == 0; });
-    }
-
-  private:
-    struct Job {
-        char* d;
-        const char* s;
-        size_t n;
-    };
-    void loop() {
-        for (;;) {
-            Job j;
-            {
-                std::unique_lock<std::mutex> g(mu_);
-                cv_.wait(g, [this] { return stop_ || !q_.empty(); });
-                if (stop_ && q_.empty()) return;
-                j = q_.back();
-                q_.pop_back();
-            }
-            std::memcpy(j.d, j.s, j.n);
-            std::lock_guard<std::mutex> g(mu_);
-            if (--pending_ == 0) done_cv_.notify_all();
-        }
-    }
-    std::vector<std::thread> th_;
-    std::vector<Job> q_;
-    size_t pending_ = 0;
-    bool stop_ = false;
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-};
-
-// counter slots in the device counter array
-enum : int {
-    C_CLS = 0,       // 12 slots
-    C_NEXT = 12,
-    C_EQ = 13,
-    C_ACTIVE = 14,
-    C_ALPHA = 15,    // round 0: max code width of the batch
-    C_L0SEG = 16,
-    C_L0TILE = 17,
-    C_L1SEG = 18,
-    C_L1TILE = 19,
-    C_STATUS = 20,
-    C_NLONG = 21,
-    C_RICE = 22,
-    C_NFIX = 23,     // LZ77 stitch fix-up tokens (statistics)
-    C_CLSE = 24,     // 12 slots: elements per small class
-    C_L0ELEM = 36,
-    C_L1ELEM = 37,
-    C_LMAX = 38,     // the round's longest large segment
-    C_CDC = 40,      // FastCDC cut count
-    C_N = 48,
-    H_RSUM = C_N,    // host mirror only (2 words): summed per-block cyclic rounds
-    H_ALPHA = C_N + 4,  // host mirror only: the batch's code width from the early alphabet pass
-    H_N = C_N + 16
-};
-
-}  // namespace
-
-struct kolm_ctx;
-namespace {
-// Milliseconds between two recorded events the device has already passed.  A batch's results
-// reach the host through coherent host words (read_spans), which the host can see before the
-// runtime has retired the events of the same stream: on hipErrorNotReady wait for the runtime
-// (no device wait is left) and ask again.  The usual case costs nothing extra.
-float event_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    hipError_t e = hipEventElapsedTime(&ms, a, b);
-    if (e == hipErrorNotReady) {
-        (void)hipGetLastError();
-        KOLM_HIP_CHECK(hipEventSynchronize(a));
-        KOLM_HIP_CHECK(hipEventSynchronize(b));
-        e = hipEventElapsedTime(&ms, a, b);
-    }
-    KOLM_HIP_CHECK(e);
-    return ms;
-}
-
-// Records a HIP event pair around the launches in its scope (timing enabled only).
-struct TScope {
-    kolm_ctx* c;
-    int fam;
-    const char* name;  // kernel symbol (as rocprof shows it, namespaces stripped)
-    u64 bytes;
-    hipEvent_t a = nullptr;
-    TScope(kolm_ctx* c_, int fam_, const char* name_, u64 bytes_);
-    ~TScope() noexcept(false);
-};
-}  // namespace
-
-struct kolm_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;  // main stream
-    hipStream_t aux = nullptr;     // second stream: Lyndon + cyclic sort chain runs beside LZ77
-    hipStream_t active = nullptr;  // stream used by launches / TScope / sync()
-    hipStream_t rp = nullptr;      // third stream: Re-Pair (candidate 9), one workgroup per block
-    bool serial = false;           // every launch of a batch on one stream (kolm_ctx_set_serial; KOLM_SERIAL=1)
-    // verify-after-encode (kolm_ctx_set_verify; KOLM_VERIFY=1): every encode batch is decoded and
-    // compared with its text before the call returns; vrep accumulates over the batches of one
-    // call (vrep.blocks = blocks checked so far), vshard = the call's first block within a
-    // multi-device encode
-    bool verify = false;
-    kolm_verify_report vrep{};
-    u32 vshard = 0;
-    // dedup (kolm_ctx_set_dedup; KOLM_DEDUP=1): every encode batch encodes each distinct block
-    // once (encode_batch below); drep accumulates over the batches of one call
-    bool dedup = false;
-    kolm_dedup_report drep{};
-    hipEvent_t evd[2] = {};        // dedup: the event pair around its kernels
-    // checksums (kolm_ctx_set_checksums; KOLM_CHECKSUMS=1): every encode batch takes the CRC-32 of
-    // its blocks on the resident text (crc_enqueue / crc_collect below); ccrc accumulates over the
-    // batches of one call.  The rest is the state of one CRC pass, used by every caller of the
-    // pair under the context lock: the table words on the device (an allocation of its own, made
-    // at the first pass: the per-batch clean-up of the named buffers never touches it), the host
-    // arrays the pass's uploads read (alive until the pass is collected), the pinned landing
-    // buffer of the raw words and the events around the kernel and behind the read-back
-    bool checksums = false;
-    std::vector<u32> ccrc;
-    struct CrcPass {
-        u32* d_tab = nullptr;
-        u32* h_raw = nullptr;
-        size_t h_cap = 0;
-        std::vector<u32> hb, scan;  // block bounds (nb + 1) and the scan of the run counts
-        u32 nb = 0;
-        // what crc_prepare leaves for crc_launch: the text, its geometry and the raw words' buffer
-        const u8* text = nullptr;
-        u64 N = 0;
-        u32 bs = 0;
-        bool var = false;
-        u32* draw = nullptr;
-        bool armed = false;     // prepared, not launched yet
-        bool launched = false;
-        hipEvent_t ev[3] = {};  // kernel start, kernel end, words on the host
-    } crc;
-    // line index (kolm_ctx_set_lines; KOLM_LINES=1, KOLM_LINES_DELIM): every encode batch counts the
-    // bytes equal to lines_delim in its blocks on the resident text (lines_prepare / lines_launch /
-    // lines_collect below: the CRC pass's shape, launched where that pass is); clines accumulates
-    // over the batches of one call.  The rest is the state of one counting pass, used by every
-    // caller under the context lock.
-    bool lines = false;
-    u32 lines_delim = 0x0A;
-    std::vector<u32> clines;
-    struct LinePass {
-        u32* h_cnt = nullptr;  // pinned landing buffer of the counts
-        size_t h_cap = 0;
-        std::vector<u32> hb, scan, pbase;  // block bounds, the scans of the run and of the piece counts (nb + 1 each)
-        u32 nb = 0;
-        const u8* text = nullptr;
-        u64 N = 0;
-        u32 bs = 0, delim = 0;
-        bool var = false;
-        bool pieces = false;    // also the 4 KiB pieces' counts ("lin_pcnt", at "lin_pbase") and their scan
-        const lin::Query* q = nullptr;  // with pieces: the queries answered behind the scan
-        u32 nq = 0;
-        u32* dcnt = nullptr;
-        bool armed = false;     // prepared, not launched yet
-        bool launched = false;
-        hipEvent_t ev[3] = {};  // kernel start, kernel end, counts on the host
-    } lin;
-    // Lyndon fast route (kolm_ctx_lyndon_report): the last batch's block count, whether the fast
-    // route ran and the stream it ran on; the route words stay in the "lyn_route" buffer
-    u32 lyn_nb = 0;
-    bool lyn_fast = false;
-    hipStream_t lyn_stream = nullptr;
-    // pinned host staging: an upload ring (input chunks) and the result buffer of
-    // kolm_compress_fixed (container bytes, valid until the next call on this context)
-    static constexpr int NSTAGE = 4;
-    u8* stage[NSTAGE] = {};
-    hipEvent_t stage_ev[NSTAGE] = {};
-    u8* h_res = nullptr;
-    size_t h_res_cap = 0, h_res_len = 0, h_res_off = 0;  // the container is h_res[off, off + len)
-    hipStream_t up = nullptr, dl = nullptr;  // kolm_compress_fixed: upload / download streams
-    hipEvent_t up_ev = nullptr;
-    std::unique_ptr<CopyPool> pool;
-    hipEvent_t evj[4] = {};        // join events
-    hipEvent_t evr[2] = {};        // Re-Pair start / done
-    hipEvent_t evg[2] = {};        // early BBWT gather: slots marked / gathered
-    hipEvent_t eva = nullptr;      // the early alphabet pass's width copied to the host
-    std::mutex mu;
-    std::map<std::string, DevBuf> bufs;
-    u32* h_cnt = nullptr;  // pinned mirror of the counters
-    // fine-grained (coherent) host words small device results are stored into by k_spans_to_host
-    // (read_spans below): RT_WORDS result words, then one sequence word per wave
-    u32* h_rt = nullptr;
-    u32* d_rt = nullptr;  // the same buffer as the device addresses it
-    u32 rt_seq = 0;
-    // pinned landing buffer of a batch's packed small results (one device-to-host copy per
-    // host round trip instead of one per array: each copy is a blit launch of ~15-25 us)
-    u32* h_tail = nullptr;
-    size_t h_tail_cap = 0;
-    u32* tail_host(size_t words) {
-        if (words > h_tail_cap) {
-            if (h_tail) KOLM_HIP_CHECK(hipHostFree(h_tail));
-            h_tail = nullptr;
-            h_tail_cap = 0;
-            const size_t cap = std::max<size_t>(words + (words >> 2), 4096);
-            KOLM_HIP_CHECK(hipHostMalloc((void**)&h_tail, cap * sizeof(u32), hipHostMallocDefault));
-            h_tail_cap = cap;
-        }
-        return h_tail;
-    }
-    hipEvent_t ev[8] = {};
-    // per-launch timing of kernel families (kolm_ctx_set_timing)
-    bool timing = false;
-    std::vector<hipEvent_t> evpool;
-    size_t evused = 0;
-    struct Pend {
-        int fam;
-        const char* name;
-        hipEvent_t a, b;
-        u64 bytes;
-        int strm;  // 0 index stream, 1 sort stream, 2 Re-Pair stream
-    };
-    int strm_of(hipStream_t s) const { return s == aux ? 1 : s == rp ? 2 : 0; }
-    std::vector<Pend> pend;
-    struct Acc {
-        double ms = 0;
-        u64 launches = 0, bytes = 0;
-        int fam = 0;   // KOLM_KT_* family of the kernel
-        int strm = 0;  // stream of its last launch (Pend::strm)
-    };
-    std::map<std::string, Acc> kacc;  // per kernel, accumulated while timing is enabled
-    // KTimer for multi-kernel launchers: events on the active stream, nested scopes allowed
-    struct Hook : KTimer {
-        kolm_ctx* c = nullptr;
-        struct Open {
-            int fam;
-            const char* name;
-            u64 bytes;
-            hipEvent_t a;
-        };
-        std::vector<Open> open;
-        void begin(int fam, const char* name, u64 bytes) override {
-            hipEvent_t a = c->ev_take();
-            KOLM_HIP_CHECK(hipEventRecord(a, c->active));
-            open.push_back({fam, name, bytes, a});
-        }
-        void end() override {
-            Open o = open.back();
-            open.pop_back();
-            hipEvent_t b = c->ev_take();
-            KOLM_HIP_CHECK(hipEventRecord(b, c->active));
-            c->pend.push_back({o.fam, o.name, o.a, b, o.bytes, c->strm_of(c->active)});
-        }
-    } hook;
-    KTimer* kt() {
-        hook.c = this;
-        return timing ? &hook : nullptr;
-    }
-    hipEvent_t ev_take() {
-        if (evused == evpool.size()) {
-            hipEvent_t e;
-            KOLM_HIP_CHECK(hipEventCreate(&e));
-            evpool.push_back(e);
-        }
-        return evpool[evused++];
-    }
-    void timing_reset() {
-        pend.clear();
-        evused = 0;
-    }
-    void timing_add(const Pend& p, kolm_stats* st) {
-        const float ms = event_ms(p.a, p.b);
-        if (st) {
-            st->kt[p.fam].ms += ms;
-            st->kt[p.fam].launches += 1;
-            st->kt[p.fam].bytes += p.bytes;
-        }
-        Acc& a = kacc[p.name];
-        a.fam = p.fam;
-        a.strm = p.strm;
-        a.ms += ms;
-        a.launches += 1;
-        a.bytes += p.bytes;
-    }
-    void timing_collect(kolm_stats* st) {
-        for (auto& p : pend) timing_add(p, st);
-        timing_reset();
-    }
-    // only the launches recorded since pend held p0 entries (the verify step, which runs after
-    // a batch's own collection or without one); st optional
-    void timing_collect_tail(size_t p0, kolm_stats* st) {
-        for (size_t i = p0; i < pend.size(); ++i) timing_add(pend[i], st);
-        pend.resize(p0);
-    }
-
-    void* raw(const char* name, size_t bytes) {
-        DevBuf& b = bufs[name];
-        if (bytes == 0) bytes = 16;
-        if (b.cap < bytes) {
-            if (b.p) KOLM_HIP_CHECK(hipFree(b.p));
-            b.p = nullptr;
-            const size_t cap = (bytes + 255) & ~(size_t)255;
-            KOLM_HIP_CHECK(hipMalloc(&b.p, cap));
-            b.cap = cap;
-        }
-        return b.p;
-    }
-    template <class T>
-    T* get(const char* name, size_t count) {
-        return static_cast<T*>(raw(name, count * sizeof(T)));
-    }
-    u64 bytes_held(const char* name) const {
-        const auto it = bufs.find(name);
-        return it == bufs.end() ? 0 : it->second.cap;
-    }
-    // Small device results back to the host (the doubling rounds' counters, the batch's
-    // offsets / winners / sizes): k_spans_to_host stores the spans into coherent host memory
-    // and then each wave's sequence word (system-scope release), and the host spins on those
-    // words — no blit dispatch and no stream query between the last kernel and the host's next
-    // launch.  A stream error, or a finished stream without the words, ends the wait with an
-    // error.  Returns the spans' words (h_rt[o[k] + j]).
-    static constexpr u32 RT_WORDS = 16384;  // h_rt: RT_WORDS result words, then 4 sequence words
-    const u32* read_spans(const kolm::PackSpans& ps, hipStream_t s) {
-        const u32 seq = ++rt_seq;
-        const u32 waves = kolm::launch_spans_to_host(ps, d_rt, d_rt + RT_WORDS, seq, s);
-        volatile u32* f = h_rt + RT_WORDS;
-        for (u32 w = 0, it = 1; w < waves; ++it) {
-            if (f[w] == seq) {
-                ++w;
-                continue;
-            }
-            if (it % 1024 == 0) {
-                const hipError_t e = hipStreamQuery(s);
-                if (e != hipErrorNotReady) {
-                    KOLM_HIP_CHECK(e);
-                    if (f[w] != seq)
-                        throw kolm::HipError(hipErrorUnknown, "result words not seen after the stream finished", __LINE__);
-                }
-            }
-            __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return h_rt;
-    }
-    static bool fits_rt(const kolm::PackSpans& ps) {
-        u64 end = 0;
-        for (int k = 0; k < 6; ++k)
-            if (ps.p[k]) end = std::max<u64>(end, (u64)ps.o[k] + ps.n[k]);
-        return end <= RT_WORDS;
-    }
-    void read_counts(u32* h, const u32* cnt, u32 n, hipStream_t s) {
-        kolm::PackSpans ps{};
-        ps.p[0] = cnt, ps.n[0] = n, ps.o[0] = 0;
-        const volatile u32* r = read_spans(ps, s);
-        for (u32 i = 0; i < n; ++i) h[i] = r[i];
-    }
-    // Host round trips (per-round counters) spin on the stream instead of sleeping in
-    // hipStreamSynchronize: the sort stream idles for the host's wake-up otherwise.
-    void sync() {
-        static const bool block = getenv("KOLM_SYNC_BLOCK") && atoi(getenv("KOLM_SYNC_BLOCK"));
-        if (block) {
-            KOLM_HIP_CHECK(hipStreamSynchronize(active));
-            return;
-        }
-        hipError_t e;
-        while ((e = hipStreamQuery(active)) == hipErrorNotReady) {
-        }
-        KOLM_HIP_CHECK(e);
-    }
-};
-
-namespace kolm {
 int ctx_device(const kolm_ctx* c) { return c->device; }
+float ev_ms(hipEvent_t a, hipEvent_t b) { return event_ms(a, b); }
 }  // namespace kolm
 
 namespace {
-
-TScope::TScope(kolm_ctx* c_, int fam_, const char* name_, u64 bytes_) : c(c_), fam(fam_), name(name_), bytes(bytes_) {
-    if (c->timing) {
-        a = c->ev_take();
-        KOLM_HIP_CHECK(hipEventRecord(a, c->active));
-    }
-}
-TScope::~TScope() noexcept(false) {
-    if (c->timing) {
-        hipEvent_t b = c->ev_take();
-        KOLM_HIP_CHECK(hipEventRecord(b, c->active));
-        c->pend.push_back({fam, name, a, b, bytes, c->strm_of(c->active)});
-    }
-}
 
 std::mutex g_mu;
 kolm_ctx* g_default = nullptr;
@@ -978,8 +550,6 @@ struct Pipeline {
     }
 };
 
-float ev_ms(hipEvent_t a, hipEvent_t b) { return event_ms(a, b); }
-
 int check_geom(u64 N, u32 bs) {
     if (N >= (1ull << 31)) {
         set_err("batch larger than 2^31-1 bytes");
@@ -1079,7 +649,6 @@ int encode_batch(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_boun
                  const int32_t* h_force, u8* d_arena, u64 arena_cap, u32* h_sizes, u32* h_method, u64* h_off,
                  kolm_stats* stats);
 void crc_launch(kolm_ctx* c, hipStream_t s);  // checksums: the prepared CRC pass, if one is armed (below)
-void lines_launch(kolm_ctx* c, hipStream_t s);  // line index: the prepared counting pass, if one is armed (below)
 int decode_blocks_host(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
                        const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap, bool with_crc,
                        const uint32_t* expect, uint32_t* got);  // kolm_decode_blocks[_crc] (with the verify step below)
@@ -1497,22 +1066,6 @@ int encode_each(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* h_bound
     return KOLM_OK;
 }
 
-template <class F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const HipError& e) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "HIP error %d (%s) at kolm_api line %d: %s", (int)e.err,
-                 hipGetErrorString(e.err), e.line, e.what);
-        set_err(buf);
-        return KOLM_EHIP;
-    } catch (const std::bad_alloc&) {
-        set_err("host allocation failed");
-        return KOLM_EHIP;
-    }
-}
-
 int ctx_create(int device, kolm_ctx** out) {
     return guarded([&] {
         int n = 0;
@@ -1556,10 +1109,14 @@ int ctx_create(int device, kolm_ctx** out) {
     });
 }
 
-kolm_ctx* need_default() {
+}  // namespace
+
+kolm_ctx* kolm::need_default() {
     std::lock_guard<std::mutex> g(g_mu);
     return g_default;
 }
+
+namespace {
 
 // start of an encode call (context lock held): the verify report covers this call's batches
 void verify_begin(kolm_ctx* c, u32 first_block = 0) {
@@ -2543,15 +2100,17 @@ static int check_decode(const uint64_t* payload_off, const uint32_t* methods, co
     return KOLM_OK;
 }
 
+}  // extern "C"
+
 // Decodes nb blocks whose payloads are resident at dpay (+ payload_off[i] - payload_off[0])
 // into dout (device).  Per-decoder block lists are built on the host; every kernel
 // runs on the context stream.  ms (optional) = device time of the decode kernels.
 // status_out (optional, the verify path): receives every block's DEC_* word instead of the call
 // failing at the first rejected block; d_obase then receives the device copy of the nb + 1
 // output offsets (valid until the next decode on the context).
-static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off, const uint32_t* methods,
-                        const uint32_t* orig_lens, u32 nb, u64 total, u8* dout, double* ms,
-                        std::vector<u32>* status_out = nullptr, const u32** d_obase = nullptr) {
+int kolm::decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off, const uint32_t* methods,
+                       const uint32_t* orig_lens, u32 nb, u64 total, u8* dout, double* ms, std::vector<u32>* status_out,
+                       const u32** d_obase) {
     hipStream_t s = c->stream;
     std::vector<u64> poff(nb + 1);
     std::vector<u32> obase(nb + 1);
@@ -2771,6 +2330,8 @@ static int decode_batch(kolm_ctx* c, const u8* dpay, const uint64_t* payload_off
     return KOLM_OK;
 }
 
+extern "C" {
+
 int kolm_decode_blocks(const uint8_t* payloads, const uint64_t* payload_off, const uint32_t* methods,
                        const uint32_t* orig_lens, uint32_t nblocks, uint8_t* out, uint64_t out_cap) {
     return decode_blocks_host(payloads, payload_off, methods, orig_lens, nblocks, out, out_cap, false, nullptr, nullptr);
@@ -2927,6 +2488,10 @@ double crc_collect(kolm_ctx* c, u32* out) {
     return ms;
 }
 
+}  // namespace
+
+namespace kolm {  // declared in kolm_ctx.h: the container readers' source file calls what follows
+
 // The pass over the blocks of lengths lens[0, n) that lie back to back at d (a decode scratch):
 // out[0, n).  Returns the kernel's device time.
 double crc_blocks_at(kolm_ctx* c, const u8* d, const u32* lens, u32 n, u32* out) {
@@ -2945,7 +2510,7 @@ double crc_blocks_at(kolm_ctx* c, const u8* d, const u32* lens, u32 n, u32* out)
 // block's number in this pass) are answered by k_delim_query behind the scan and their results
 // come back with the counts, in the same copy.  One pass at a time per context (its lock is held).
 void lines_prepare(kolm_ctx* c, const u8* d_text, u64 N, u32 bs, const u32* hb, u32 nb, u32 delim, bool pieces,
-                   const lin::Query* q = nullptr, u32 nq = 0) {
+                   const lin::Query* q, u32 nq) {
     kolm_ctx::LinePass& p = c->lin;
     for (auto& e : p.ev)
         if (!e) KOLM_HIP_CHECK(hipEventCreate(&e));
@@ -3041,7 +2606,7 @@ void lines_launch(kolm_ctx* c, hipStream_t s) {
 // The counts of the pass enqueued last: out[0, nb), and its queries' results: res[0, nq).  Waits
 // for the read-back's event.  Returns the kernels' device time and, with timing on, adds the
 // counting launch to the per-kernel table.
-double lines_collect(kolm_ctx* c, u32* out, u32* res = nullptr) {
+double lines_collect(kolm_ctx* c, u32* out, u32* res) {
     kolm_ctx::LinePass& p = c->lin;
     double ms = 0.0;
     if (p.launched) {
@@ -3069,6 +2634,33 @@ void checksum_message(u32 block, u32 method, u32 expected, u32 got) {
     snprintf(msg, sizeof msg, "checksum: block %u (method %u): expected CRC-32 %08x, got %08x", block, method, expected, got);
     set_err(msg);
 }
+
+// A container's table of contents for the entry points that take a whole container: at most
+// 65 536 blocks (kolm_toc_read's capacity here), the arrays cut to the block count.
+int toc_load(const uint8_t* container, uint64_t cn, Toc& t) {
+    u32 fields[4] = {};
+    std::vector<u32> methods(65536), lens(65536);
+    std::vector<u64> poff(65537);
+    if (int rc = kolm_toc_read(container, cn, fields, &t.start, methods.data(), lens.data(), poff.data(), 65536)) return rc;
+    t.mode = fields[0], t.size_field = fields[1], t.total = fields[2], t.nb = fields[3];
+    methods.resize(t.nb), lens.resize(t.nb), poff.resize((size_t)t.nb + 1);
+    t.methods.swap(methods), t.lens.swap(lens), t.poff.swap(poff);
+    t.sum = 0;
+    for (u32 l : t.lens) t.sum += l;
+    return KOLM_OK;
+}
+
+int toc_check_length(const Toc& t) {
+    if (t.sum == t.total) return KOLM_OK;
+    char msg[96];
+    snprintf(msg, sizeof msg, "Length mismatch: got %llu, expect %llu", (unsigned long long)t.sum, (unsigned long long)t.total);
+    set_err(msg);
+    return KOLM_EFORMAT;
+}
+
+}  // namespace kolm
+
+namespace {
 
 // Blocks [0, nb) of d_data (block i = [bounds[i], bounds[i + 1])) against their payloads at
 // d_pay + (poff[i] - poff[0]); both device-resident and complete as far as c->stream sees.
@@ -3324,14 +2916,11 @@ int kolm_verify_container(const uint8_t* container, uint64_t cn, const uint8_t* 
     if ((!container && cn) || (!data && n)) return KOLM_EARG;
     kolm_verify_report r{};
     if (rep) *rep = r;
-    u32 fields[4] = {};
-    u64 start = 0;
-    std::vector<u32> methods(65536), lens(65536);
-    std::vector<u64> poff(65537);
-    if (int rc = kolm_toc_read(container, cn, fields, &start, methods.data(), lens.data(), poff.data(), 65536)) return rc;
-    const u32 nb = fields[3];
+    Toc t;
+    if (int rc = toc_load(container, cn, t)) return rc;
+    const u32 nb = t.nb;
     r.blocks = nb;
-    if (fields[2] != n) {
+    if (t.total != n) {
         r.bad_blocks = nb;
         r.first_bad_reason = KOLM_VR_LENGTH;
         if (rep) *rep = r;
@@ -3343,26 +2932,27 @@ int kolm_verify_container(const uint8_t* container, uint64_t cn, const uint8_t* 
     }
     r.blocks = 0;
     if (nb == 0) return KOLM_OK;
-    std::vector<u64> bounds((size_t)nb + 1, 0);
-    for (u32 i = 0; i < nb; ++i) bounds[i + 1] = bounds[i] + lens[i];
-    if (bounds[nb] != n) {  // the TOC's lengths do not add up to total_len
+    // unlike opening a reader and kolm_check_container (toc_check_length), lengths that do not add up are a verify result here
+    if (t.sum != n) {
         r.bad_blocks = nb;
         r.blocks = nb;
         r.first_bad_reason = KOLM_VR_LENGTH;
         if (rep) *rep = r;
         return KOLM_OK;
     }
+    std::vector<u64> bounds((size_t)nb + 1, 0);
+    for (u32 i = 0; i < nb; ++i) bounds[i + 1] = bounds[i] + t.lens[i];
     int rc = guarded([&] {
         std::lock_guard<std::mutex> g(c->mu);
         KOLM_HIP_CHECK(hipSetDevice(c->device));
         c->timing_reset();
-        const u64 ptotal = poff[nb] - poff[0];
+        const u64 ptotal = t.poff[nb] - t.poff[0];
         u8* dpay = c->get<u8>("vfy_pay", ptotal + 64);
         u8* ddat = c->get<u8>("vfy_data", n + 64);
         if (ptotal)
-            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, container + start + poff[0], ptotal, hipMemcpyHostToDevice, c->stream));
+            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, container + t.start + t.poff[0], ptotal, hipMemcpyHostToDevice, c->stream));
         if (n) KOLM_HIP_CHECK(hipMemcpyAsync(ddat, data, n, hipMemcpyHostToDevice, c->stream));
-        return verify_run(c, ddat, bounds.data(), nb, dpay, poff.data(), methods.data(), first_bad, 0, r, nullptr);
+        return verify_run(c, ddat, bounds.data(), nb, dpay, t.poff.data(), t.methods.data(), first_bad, 0, r, nullptr);
     });
     if (rep) *rep = r;
     return rc;
@@ -3370,62 +2960,7 @@ int kolm_verify_container(const uint8_t* container, uint64_t cn, const uint8_t* 
 
 }  // extern "C"
 
-// ---- random-access reads: decode the blocks a range touches, pack the ranges on the device ----
-struct kolm_reader {
-    kolm_ctx* c = nullptr;
-    u32 mode = 0, size_field = 0, nb = 0;
-    u64 total = 0, pbytes = 0;
-    std::vector<u32> methods, lens;
-    std::vector<u64> poff, starts;  // payload offsets / decoded block starts, nb + 1 entries each
-    // the payload area, resident (its own allocation: it outlives the calls).  A source of
-    // k_range_gather (payload compaction): hipMalloc aligns it to 256 bytes and it is padded by
-    // 64 + 16 bytes, the decoders' read-ahead plus the gather's last aligned word.
-    u8* dpay = nullptr;
-    // the blocks' expected CRC-32 (kolm_reader_set_checksums): nb words, or empty = reads are not checked
-    std::vector<u32> crcs;
-    // the line index (kolm_reader_set_lines / kolm_reader_index_lines): the blocks' counts of bytes
-    // equal to ldelim, nb words, when has_lines
-    bool has_lines = false;
-    u32 ldelim = 0x0A;
-    std::vector<u32> lcounts;
-    // the result of the last kolm_reader_find: absolute offsets and pattern indices, in
-    // (offset, pattern) order (kolm_reader_find_copy)
-    std::vector<u64> f_offs;
-    std::vector<u8> f_which;
-    // the result of the last kolm_reader_find_set (kolm_reader_find_copy32); either call empties
-    // the other's result
-    std::vector<u64> fs_offs;
-    std::vector<u32> fs_which;
-};
-
 namespace {
-
-// Uploads a segment table with the exclusive scan of its item counts and launches k_range_gather
-// on c->stream between the event pair (e0, e1).  dst: the segments' destination base.
-void gather_segments(kolm_ctx* c, const char* name, const u8* src, u8* dst, const rng::Seg* segs, u32 nseg,
-                     std::vector<u32>& scan, hipEvent_t e0, hipEvent_t e1) {
-    hipStream_t s = c->stream;
-    scan.assign((size_t)nseg + 1, 0);
-    u64 items = 0, bytes = 0;
-    for (u32 i = 0; i < nseg; ++i) {
-        const u32 dmis = (u32)((reinterpret_cast<uintptr_t>(dst) + segs[i].dst) & (rng::WORD - 1));
-        items += rng::items(dmis, segs[i].len);
-        bytes += segs[i].len;
-        if (items > 0xFFFFFFFFull) throw kolm::HipError(hipErrorInvalidValue, "more than 2^32 - 1 gather items", __LINE__);
-        scan[i + 1] = (u32)items;
-    }
-    const std::string nseg_name = std::string(name) + "_seg", nscan_name = std::string(name) + "_scan";
-    rng::Seg* dseg = c->get<rng::Seg>(nseg_name.c_str(), nseg);
-    u32* dscan = c->get<u32>(nscan_name.c_str(), (size_t)nseg + 1);
-    KOLM_HIP_CHECK(hipMemcpyAsync(dseg, segs, sizeof(rng::Seg) * nseg, hipMemcpyHostToDevice, s));
-    KOLM_HIP_CHECK(hipMemcpyAsync(dscan, scan.data(), sizeof(u32) * ((size_t)nseg + 1), hipMemcpyHostToDevice, s));
-    KOLM_HIP_CHECK(hipEventRecord(e0, s));
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_range_gather", 2 * bytes);
-        launch_range_gather(src, dst, dseg, dscan, nseg, items, s);
-    }
-    KOLM_HIP_CHECK(hipEventRecord(e1, s));
-}
 
 // ---- dedup: encode repeated blocks once (dedup_core.h, k_dedup.hip, kolm_dedup.cpp) ----
 // What the detection finds in one batch.
@@ -3810,861 +3345,6 @@ int kolm_find_duplicates_device(kolm_ctx* c, const void* d_data, const uint64_t*
     return rc;
 }
 
-}  // extern "C"
-
-namespace {
-
-// out (host) or d_out (device) receives the packed ranges.  Context lock not held on entry.
-int reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nr, uint8_t* out, void* d_out,
-                uint64_t out_cap, kolm_read_stats* stats) {
-    if (stats) *stats = kolm_read_stats{};
-    if (!r || !r->c || (nr && (!offs || !lens))) return KOLM_EARG;
-    // every argument check before the first launch: the plan (ranges), the output, the selected blocks
-    RangePlan p;
-    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, offs, lens, nr, 0, p)) return rc;
-    u64 want = 0;
-    for (u32 i = 0; i < nr; ++i) want += lens[i];
-    if (want > out_cap) {
-        set_err("output capacity too small");
-        return KOLM_ECAP;
-    }
-    if (want && !out && !d_out) return KOLM_EARG;
-    kolm_read_stats st{};
-    st.ranges = nr;
-    st.bytes_returned = want;
-    st.blocks_decoded = (u32)p.sel.size();
-    st.groups = (u32)p.group_first.size() - 1;
-    for (u32 b : p.sel) {
-        const u32 m = r->methods[b];
-        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
-            r->lens[b] >= (1u << 31)) {
-            char msg[128];
-            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        st.bytes_decoded += r->lens[b];
-    }
-    if (p.sel.empty()) {
-        if (stats) *stats = st;
-        return KOLM_OK;
-    }
-    kolm_ctx* c = r->c;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        hipStream_t s = c->stream;
-        c->active = s;
-        // Checked reads write nothing to the caller's buffer on a mismatch: with several groups the
-        // ranges are packed in the context's own buffer and copied once every group has passed.
-        const bool checked = !r->crcs.empty();
-        const bool staged = checked && d_out && p.group_first.size() > 2;
-        u8* dout = d_out && !staged ? static_cast<u8*>(d_out) : c->get<u8>("rd_out", want + 64);
-        std::vector<u32> gm, gl, status, scan, words;
-        std::vector<u64> gp;
-        std::vector<rng::Seg> runs;
-        for (u32 g = 0; g + 1 < p.group_first.size(); ++g) {
-            const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
-            gm.resize(n), gl.resize(n), gp.assign((size_t)n + 1, 0);
-            runs.clear();
-            u64 tot = 0;
-            for (u32 i = i0; i < i1; ++i) {
-                const u32 b = p.sel[i];
-                gm[i - i0] = r->methods[b];
-                gl[i - i0] = r->lens[b];
-                tot += r->lens[b];
-                const u64 plen = r->poff[b + 1] - r->poff[b];
-                if (i == i0 || b != p.sel[i - 1] + 1) runs.push_back(rng::Seg{r->poff[b] - r->poff[0], gp[i - i0], 0});
-                runs.back().len += plen;
-                gp[i - i0 + 1] = gp[i - i0] + plen;
-            }
-            // one run is decoded where it lies; several are gathered into a staging buffer first
-            // (decode_batch takes contiguous payloads).  "rd_pay": read-ahead padding as dec_pay.
-            const u8* pay = r->dpay + runs[0].src;
-            const bool compact = runs.size() > 1;
-            if (compact) {
-                u8* stage = c->get<u8>("rd_pay", gp[n] + 64);
-                gather_segments(c, "rd_c", r->dpay, stage, runs.data(), (u32)runs.size(), scan, c->ev[4], c->ev[5]);
-                pay = stage;
-                ++st.compactions;
-            }
-            // the decode scratch, a source of k_range_gather: 256-byte aligned (hipMalloc), padded
-            // by the decoders' 64 bytes and the gather's last aligned 16-byte word
-            u8* dec = c->get<u8>("rd_dec", tot + 64 + rng::WORD);
-            double ms = 0.0;
-            if (int e = decode_batch(c, pay, gp.data(), gm.data(), gl.data(), n, tot, dec, &ms, &status)) return e;
-            st.ms_decode += ms;
-            if (compact) st.ms_gather += ev_ms(c->ev[4], c->ev[5]);  // retired: decode_batch drained the stream
-            for (u32 i = 0; i < n; ++i)
-                if (status[i]) {
-                    char msg[128];
-                    snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], gm[i],
-                             status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
-                    set_err(msg);
-                    return KOLM_EARG;
-                }
-            if (checked) {  // the group's blocks lie back to back in the scratch: one pass, one round trip
-                words.resize(n);
-                crc_blocks_at(c, dec, gl.data(), n, words.data());
-                for (u32 i = 0; i < n; ++i) {
-                    const u32 b = p.sel[i0 + i];
-                    if (words[i] != r->crcs[b]) {
-                        checksum_message(b, gm[i], r->crcs[b], words[i]);
-                        return KOLM_ECHECKSUM;
-                    }
-                }
-            }
-            const u32 s0 = p.group_seg[g], s1 = p.group_seg[g + 1];
-            if (s1 > s0) {
-                gather_segments(c, "rd_g", dec, dout, p.segs.data() + s0, s1 - s0, scan, c->ev[2], c->ev[3]);
-                c->sync();  // the next group reuses the scratch tables; the events are retired
-                st.ms_gather += ev_ms(c->ev[2], c->ev[3]);
-            }
-        }
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        if (staged && want) {  // on the context's stream and waited for: a device-to-device hipMemcpy does not wait
-            KOLM_HIP_CHECK(hipMemcpyAsync(d_out, dout, want, hipMemcpyDeviceToDevice, s));
-            c->sync();
-        }
-        if (!d_out && want) KOLM_HIP_CHECK(hipMemcpy(out, dout, want, hipMemcpyDeviceToHost));
-        return KOLM_OK;
-    });
-    if (stats) *stats = st;
-    return rc;
-}
-
-}  // namespace
-
-// ---- search of decoded bytes on the device (find_core.h, k_find.hip) ----
-namespace {
-
-u64 find_stage_bytes() {  // read per call, like KOLM_READ_BYTES
-    u64 v = fnd::STAGE_DEFAULT;
-    if (const char* e = getenv("KOLM_FIND_STAGE")) v = std::max<u64>(1, strtoull(e, nullptr, 10));
-    return v;
-}
-
-// np patterns, pattern i = pats[pat_off[i], pat_off[i + 1]); L = the longest
-int find_check_pats(const char* who, const uint8_t* pats, const uint32_t* pat_off, u32 np, u32* L) {
-    char msg[160];
-    if (np < 1 || np > KOLM_FIND_MAX_PATTERNS) {
-        snprintf(msg, sizeof msg, "%s: %u patterns (1..%u are allowed)", who, np, (u32)KOLM_FIND_MAX_PATTERNS);
-        set_err(msg);
-        return KOLM_EARG;
-    }
-    if (!pats || !pat_off) return KOLM_EARG;
-    *L = 0;
-    for (u32 i = 0; i < np; ++i) {
-        if (pat_off[i + 1] <= pat_off[i]) {
-            snprintf(msg, sizeof msg, "%s: pattern %u is empty", who, i);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        const u32 len = pat_off[i + 1] - pat_off[i];
-        if (len > KOLM_FIND_MAX_LEN) {
-            snprintf(msg, sizeof msg, "%s: pattern %u has %u bytes (at most %u)", who, i, len, (u32)KOLM_FIND_MAX_LEN);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        *L = std::max(*L, len);
-    }
-    return KOLM_OK;
-}
-
-const fnd::Pats* find_upload_pats(kolm_ctx* c, const uint8_t* pats, const uint32_t* pat_off, u32 np, fnd::Pats& hp) {
-    fnd::make_pats(pats, pat_off, np, hp);
-    fnd::Pats* dp = c->get<fnd::Pats>("fd_pats", 1);
-    KOLM_HIP_CHECK(hipMemcpyAsync(dp, &hp, sizeof hp, hipMemcpyHostToDevice, c->stream));
-    return dp;
-}
-
-// One scan buffer buf [0, n) on c->stream: count, scan, one round trip for the totals, then the
-// emit launches (none when nothing is to be returned).  counts [np] accumulate; (base + position,
-// pattern) are appended to offs / which until `limit` results are held.  more_than (optional):
-// when the group would return more than *more_than results, nothing is emitted and it is set to
-// that number.
-void find_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fnd::Pats* dP, u32 np, u64 base, u64 limit,
-                u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms,
-                u64* more_than = nullptr) {
-    const u32 ntiles = fnd::tiles(n);
-    if (!ntiles) return;
-    hipStream_t s = c->stream;
-    u32* cnt = c->get<u32>("fd_cnt", (size_t)(np + 1) * ntiles);
-    u64* tot = c->get<u64>("fd_tot", fnd::MAX_PATTERNS + 1);
-    u64* tscan = c->get<u64>("fd_scan", (size_t)ntiles + 1);
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_find_count", n);
-        launch_find_count(buf, n, lo, shi, dP, np, cnt, s);
-    }
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)(np + 1) * ntiles);
-        launch_find_scan(cnt, ntiles, np, tot, tscan, s);
-    }
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
-    u64 htot[fnd::MAX_PATTERNS + 1] = {};
-    KOLM_HIP_CHECK(hipMemcpyAsync(htot, tot, sizeof(u64) * (np + 1), hipMemcpyDeviceToHost, s));
-    c->sync();
-    ms += ev_ms(c->ev[6], c->ev[7]);
-    for (u32 i = 0; i < np; ++i) counts[i] += htot[i];
-    const u64 total = htot[np];
-    const u64 want = std::min<u64>(total, limit > offs.size() ? limit - offs.size() : 0);
-    if (more_than && want > *more_than) {
-        *more_than = want;
-        return;
-    }
-    if (!want) return;
-    const u64 cap = std::min<u64>(fnd::stage_records(find_stage_bytes(), np), 0xFFFFFFFFull);
-    const u64 slots = std::min<u64>(cap, total);  // no launch holds more than either
-    u32* dpos = c->get<u32>("fd_pos", slots);
-    u8* dwhich = c->get<u8>("fd_which", slots);
-    // everything fits one launch and all of it is wanted: the tile scan stays on the device
-    const bool one = want == total && total <= cap;
-    std::vector<u64> hscan;
-    if (!one) {
-        hscan.resize((size_t)ntiles + 1);
-        KOLM_HIP_CHECK(hipMemcpyAsync(hscan.data(), tscan, sizeof(u64) * hscan.size(), hipMemcpyDeviceToHost, s));
-        c->sync();
-    }
-    std::vector<u32> hpos;
-    std::vector<u8> hwhich;
-    u64 got = 0;
-    for (u32 t0 = 0; got < want;) {
-        u32 t1 = ntiles;
-        u64 recs = total;
-        if (!one) {
-            while (hscan[t0 + 1] == hscan[t0]) ++t0;
-            t1 = fnd::emit_cut(hscan.data(), ntiles, t0, cap, want);
-            recs = hscan[t1] - hscan[t0];
-        }
-        KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
-        {
-            TScope t(c, KOLM_KT_EMIT, "k_find_emit", (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
-            launch_find_emit(buf, n, lo, shi, dP, np, t0, t1, tscan, dpos, dwhich, (u32)slots, s);
-        }
-        KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
-        const u64 take = std::min<u64>(recs, want - got);
-        hpos.resize(take), hwhich.resize(take);
-        KOLM_HIP_CHECK(hipMemcpyAsync(hpos.data(), dpos, sizeof(u32) * take, hipMemcpyDeviceToHost, s));
-        KOLM_HIP_CHECK(hipMemcpyAsync(hwhich.data(), dwhich, take, hipMemcpyDeviceToHost, s));
-        c->sync();
-        ms += ev_ms(c->ev[6], c->ev[7]);
-        for (u64 k = 0; k < take; ++k) offs.push_back(base + hpos[k]);
-        which.insert(which.end(), hwhich.begin(), hwhich.end());
-        got += take;
-        t0 = t1;
-        ++launches;
-    }
-}
-
-// The checks of a reader's search that precede every launch: the window, and that the device
-// decodes every block that holds a byte of it.  Fills the plan and the stats' block figures.
-int find_plan(const char* who, kolm_reader* r, u64 lo, u64 hi, RangePlan& p, kolm_find_stats& st) {
-    if (lo > hi || hi > r->total) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: the window [%llu, %llu) is not inside the container's %llu bytes", who,
-                 (unsigned long long)lo, (unsigned long long)hi, (unsigned long long)r->total);
-        set_err(msg);
-        return KOLM_EARG;
-    }
-    const u64 wlen = hi - lo;
-    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, &lo, &wlen, 1, 0, p)) return rc;
-    st.blocks_decoded = (u32)p.sel.size();
-    st.groups = (u32)p.group_first.size() - 1;
-    for (u32 b : p.sel) {
-        const u32 m = r->methods[b];
-        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
-            r->lens[b] >= (1u << 31)) {
-            char msg[128];
-            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        st.bytes_decoded += r->lens[b];
-    }
-    return KOLM_OK;
-}
-
-// The group loop of a reader's search (the caller holds the context's lock and has selected the
-// device): the plan's blocks are decoded group by group -- payload runs, compaction, decode_batch,
-// status and checksum checks -- each group's bytes behind the carry of the groups before it, and
-// search(scan buffer, its fnd::GroupScan) runs on every scan buffer in stream order.  L: the
-// longest pattern (the hold-back).
-template <class F>
-int find_over_groups(kolm_reader* r, const RangePlan& p, u64 lo, u64 hi, u32 L, kolm_find_stats& st, F&& search) {
-    kolm_ctx* c = r->c;
-    hipStream_t s = c->stream;
-    const bool checked = !r->crcs.empty();
-    u8* keep = c->get<u8>("fd_carry", fnd::MAX_LEN);  // the carry between two groups' scan buffers
-    std::vector<u32> gm, gl, status, scan, words;
-    std::vector<u64> gp;
-    std::vector<rng::Seg> runs;
-    u64 S = lo;
-    u32 carry = 0;
-    const u32 ng = (u32)p.group_first.size() - 1;
-    for (u32 g = 0; g < ng; ++g) {
-        const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
-        gm.resize(n), gl.resize(n), gp.assign((size_t)n + 1, 0);
-        runs.clear();
-        u64 tot = 0;
-        for (u32 i = i0; i < i1; ++i) {
-            const u32 b = p.sel[i];
-            gm[i - i0] = r->methods[b];
-            gl[i - i0] = r->lens[b];
-            tot += r->lens[b];
-            const u64 plen = r->poff[b + 1] - r->poff[b];
-            if (i == i0 || b != p.sel[i - 1] + 1) runs.push_back(rng::Seg{r->poff[b] - r->poff[0], gp[i - i0], 0});
-            runs.back().len += plen;
-            gp[i - i0 + 1] = gp[i - i0] + plen;
-        }
-        const u8* pay = r->dpay + runs[0].src;
-        const bool compact = runs.size() > 1;
-        if (compact) {  // as reads do: several payload runs are gathered first
-            u8* stage = c->get<u8>("rd_pay", gp[n] + 64);
-            gather_segments(c, "rd_c", r->dpay, stage, runs.data(), (u32)runs.size(), scan, c->ev[4], c->ev[5]);
-            pay = stage;
-        }
-        // the scan buffer: room for the carry (it ends at a 256-byte boundary), the group's
-        // decoded bytes there, padded as "rd_dec" is (the decoders' 64 bytes, the last aligned word)
-        u8* fb = c->get<u8>("fd_buf", fnd::MAX_LEN + tot + 64 + rng::WORD);
-        u8* dec = fb + fnd::MAX_LEN;
-        if (carry) KOLM_HIP_CHECK(hipMemcpyAsync(dec - carry, keep, carry, hipMemcpyDeviceToDevice, s));
-        double ms = 0.0;
-        if (int e = decode_batch(c, pay, gp.data(), gm.data(), gl.data(), n, tot, dec, &ms, &status)) return e;
-        st.ms_decode += ms;
-        for (u32 i = 0; i < n; ++i)
-            if (status[i]) {
-                char msg[128];
-                snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], gm[i],
-                         status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
-                set_err(msg);
-                return KOLM_EARG;
-            }
-        if (checked) {
-            words.resize(n);
-            crc_blocks_at(c, dec, gl.data(), n, words.data());
-            for (u32 i = 0; i < n; ++i) {
-                const u32 b = p.sel[i0 + i];
-                if (words[i] != r->crcs[b]) {
-                    checksum_message(b, gm[i], r->crcs[b], words[i]);
-                    return KOLM_ECHECKSUM;
-                }
-            }
-        }
-        const u64 a = r->starts[p.sel[i0]], b = r->starts[p.sel[i1 - 1] + 1];
-        const fnd::GroupScan gs = fnd::group_scan(S, a, b, L, g + 1 == ng, hi);
-        st.bytes_scanned += gs.n;
-        search(dec - gs.carry, gs);
-        S = gs.S_next;
-        carry = (u32)(b - S);  // < L: the bytes [S, b) end the scan buffer
-        if (g + 1 < ng && carry) {
-            KOLM_HIP_CHECK(hipMemcpyAsync(keep, dec + tot - carry, carry, hipMemcpyDeviceToDevice, s));
-            c->sync();  // the next group may move the scan buffer
-        }
-    }
-    return KOLM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int kolm_find_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t* pats, const uint32_t* pat_off, uint32_t np,
-                     uint64_t max_results, uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap,
-                     uint64_t* nfound, double* ms) {
-    if (ms) *ms = 0.0;
-    if (nfound) *nfound = 0;
-    if (!c || !counts || !nfound) return KOLM_EARG;
-    u32 L = 0;
-    if (int rc = find_check_pats("kolm_find_device", pats, pat_off, np, &L)) return rc;
-    if (n >= (1ull << 31)) {
-        set_err("kolm_find_device: the buffer must be smaller than 2^31 bytes");
-        return KOLM_EARG;
-    }
-    if ((n && !d_data) || (cap && (!offs || (!which && np > 1)))) return KOLM_EARG;
-    for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    if (n == 0) return KOLM_OK;
-    return guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        c->active = c->stream;
-        fnd::Pats hp;
-        const fnd::Pats* dP = find_upload_pats(c, pats, pat_off, np, hp);
-        std::vector<u64> o;
-        std::vector<u8> w;
-        u32 launches = 0;
-        double t = 0.0;
-        u64 more = cap;
-        find_group(c, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, dP, np, 0, max_results, counts, o, w, launches, t,
-                   &more);
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        if (ms) *ms = t;
-        if (more > cap) {
-            *nfound = more;
-            set_err("kolm_find_device: result capacity too small");
-            return KOLM_ECAP;
-        }
-        *nfound = o.size();
-        std::copy(o.begin(), o.end(), offs);
-        if (which) std::copy(w.begin(), w.end(), which);
-        return KOLM_OK;
-    });
-}
-
-int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, uint64_t lo, uint64_t hi,
-                     uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
-    if (stats) *stats = kolm_find_stats{};
-    if (nfound) *nfound = 0;
-    if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
-    // every argument check before the first launch: the patterns, the window, the selected blocks
-    u32 L = 0;
-    if (int rc = find_check_pats("kolm_reader_find", pats, pat_off, np, &L)) return rc;
-    RangePlan p;
-    kolm_find_stats st{};
-    st.patterns = np;
-    if (int rc = find_plan("kolm_reader_find", r, lo, hi, p, st)) return rc;
-    for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    kolm_ctx* c = r->c;
-    std::vector<u64> offs;
-    std::vector<u8> which;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
-        if (p.sel.empty()) return KOLM_OK;
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        hipStream_t s = c->stream;
-        c->active = s;
-        fnd::Pats hp;
-        const fnd::Pats* dP = find_upload_pats(c, pats, pat_off, np, hp);
-        if (int e = find_over_groups(r, p, lo, hi, L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
-                find_group(c, buf, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which, st.emit_launches,
-                           st.ms_find);
-            }))
-            return e;
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        return KOLM_OK;
-    });
-    if (rc) {  // no results leave a failed call
-        for (u32 i = 0; i < np; ++i) counts[i] = 0;
-        if (stats) *stats = st;
-        return rc;
-    }
-    for (u32 i = 0; i < np; ++i) st.matches += counts[i];
-    st.returned = offs.size();
-    *nfound = offs.size();
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.swap(offs), r->f_which.swap(which);
-    }
-    if (stats) *stats = st;
-    return KOLM_OK;
-}
-
-int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint8_t* which) {
-    if (!r || !r->c) return KOLM_EARG;
-    std::lock_guard<std::mutex> g(r->c->mu);
-    if (first > r->f_offs.size() || n > r->f_offs.size() - first) {
-        set_err("kolm_reader_find_copy: more results than the last find holds");
-        return KOLM_EARG;
-    }
-    if (n && !offs) return KOLM_EARG;
-    std::copy(r->f_offs.begin() + first, r->f_offs.begin() + first + n, offs);
-    if (which) std::copy(r->f_which.begin() + first, r->f_which.begin() + first + n, which);
-    return KOLM_OK;
-}
-
-}  // extern "C"
-
-// ---- search for a prepared pattern set (findset_core.h, k_findset.hip) ----
-// The set owns its device tables (its own allocations: the context's named scratch may move with
-// the next call) and the per-pattern counters of a call.
-struct kolm_patset {
-    kolm_ctx* c = nullptr;
-    fst::Info info{};
-    fst::Set dev{};  // the tables on the device
-    u32 *d_filter = nullptr;
-    fst::Slot* d_slots = nullptr;
-    fst::Entry* d_entries = nullptr;
-    u64 *d_blob = nullptr, *d_pcnt = nullptr;
-};
-
-namespace {
-
-void patset_release(kolm_patset* ps) {
-    for (void* q : {(void*)ps->d_filter, (void*)ps->d_slots, (void*)ps->d_entries, (void*)ps->d_blob, (void*)ps->d_pcnt})
-        if (q) (void)hipFree(q);
-}
-
-// find_group for a set.  which: the pattern indices, 32 bits each; the per-pattern counters stay
-// on the device (ps->d_pcnt) until the call ends.
-void findset_group(kolm_ctx* c, const kolm_patset* ps, const u8* buf, u32 n, u32 lo, u32 shi, u64 base, u64 limit,
-                   u64& matches, std::vector<u64>& offs, std::vector<u32>& which, u32& launches, double& ms,
-                   u64* more_than = nullptr) {
-    const u32 ntiles = fnd::tiles(n);
-    if (!ntiles) return;
-    hipStream_t s = c->stream;
-    u32* cnt = c->get<u32>("fs_cnt", ntiles);
-    u64* tot = c->get<u64>("fs_tot", 1);
-    u64* tscan = c->get<u64>("fs_scan", (size_t)ntiles + 1);
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_findset_count", n);
-        launch_findset_count(buf, n, lo, shi, ps->dev, cnt, ps->d_pcnt, s);
-    }
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)ntiles);
-        launch_find_scan(cnt, ntiles, 0, tot, tscan, s);
-    }
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
-    u64 total = 0;
-    KOLM_HIP_CHECK(hipMemcpyAsync(&total, tot, sizeof(u64), hipMemcpyDeviceToHost, s));
-    c->sync();
-    ms += ev_ms(c->ev[6], c->ev[7]);
-    matches += total;
-    const u64 want = std::min<u64>(total, limit > offs.size() ? limit - offs.size() : 0);
-    if (more_than && want > *more_than) {
-        *more_than = want;
-        return;
-    }
-    if (!want) return;
-    const u64 cap = std::min<u64>(fst::stage_records(find_stage_bytes(), ps->info.np), 0xFFFFFFFFull);
-    const u64 slots = std::min<u64>(cap, total);  // no launch holds more than either
-    uint2* drec = c->get<uint2>("fs_rec", slots);
-    const bool one = want == total && total <= cap;  // one launch: the tile scan stays on the device
-    std::vector<u64> hscan;
-    if (!one) {
-        hscan.resize((size_t)ntiles + 1);
-        KOLM_HIP_CHECK(hipMemcpyAsync(hscan.data(), tscan, sizeof(u64) * hscan.size(), hipMemcpyDeviceToHost, s));
-        c->sync();
-    }
-    std::vector<uint2> hrec;
-    u64 got = 0;
-    for (u32 t0 = 0; got < want;) {
-        u32 t1 = ntiles;
-        u64 recs = total;
-        if (!one) {
-            while (hscan[t0 + 1] == hscan[t0]) ++t0;
-            t1 = fnd::emit_cut(hscan.data(), ntiles, t0, cap, want);
-            recs = hscan[t1] - hscan[t0];
-        }
-        KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
-        {
-            TScope t(c, KOLM_KT_EMIT, "k_findset_emit", (u64)(t1 - t0) * fnd::TILE + fst::REC_BYTES * recs);
-            launch_findset_emit(buf, n, lo, shi, ps->dev, t0, t1, tscan, drec, (u32)slots, s);
-        }
-        KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
-        const u64 take = std::min<u64>(recs, want - got);
-        hrec.resize(take);
-        KOLM_HIP_CHECK(hipMemcpyAsync(hrec.data(), drec, sizeof(uint2) * take, hipMemcpyDeviceToHost, s));
-        c->sync();
-        ms += ev_ms(c->ev[6], c->ev[7]);
-        for (u64 k = 0; k < take; ++k) offs.push_back(base + hrec[k].x), which.push_back(hrec[k].y);
-        got += take;
-        t0 = t1;
-        ++launches;
-    }
-}
-
-void findset_zero_counts(kolm_ctx* c, const kolm_patset* ps) {
-    KOLM_HIP_CHECK(hipMemsetAsync(ps->d_pcnt, 0, sizeof(u64) * ps->info.np, c->stream));
-}
-
-// the counters back once, at the end of a call (counts may be NULL)
-void findset_read_counts(kolm_ctx* c, const kolm_patset* ps, u64* counts) {
-    if (!counts) return;
-    KOLM_HIP_CHECK(hipMemcpyAsync(counts, ps->d_pcnt, sizeof(u64) * ps->info.np, hipMemcpyDeviceToHost, c->stream));
-    c->sync();
-}
-
-}  // namespace
-
-extern "C" {
-
-int kolm_patset_create(kolm_ctx* c, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, kolm_patset** out) {
-    if (!out) return KOLM_EARG;
-    *out = nullptr;
-    if (!c) c = need_default();
-    if (!c) return KOLM_ENOINIT;
-    char msg[160];
-    if (np < 1 || np > KOLM_FIND_SET_MAX_PATTERNS) {
-        snprintf(msg, sizeof msg, "kolm_patset_create: %u patterns (1..%u are allowed)", np, (u32)KOLM_FIND_SET_MAX_PATTERNS);
-        set_err(msg);
-        return KOLM_EARG;
-    }
-    if (!pats || !pat_off) return KOLM_EARG;
-    for (u32 i = 0; i < np; ++i) {
-        if (pat_off[i + 1] <= pat_off[i]) {
-            snprintf(msg, sizeof msg, "kolm_patset_create: pattern %u is empty", i);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        const u32 len = pat_off[i + 1] - pat_off[i];
-        if (len > KOLM_FIND_MAX_LEN) {
-            snprintf(msg, sizeof msg, "kolm_patset_create: pattern %u has %u bytes (at most %u)", i, len,
-                     (u32)KOLM_FIND_MAX_LEN);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-    }
-    fst::Tables T;
-    u32 dup[2] = {0, 0};
-    if (!fst::build(pats, pat_off, np, T, dup)) {
-        snprintf(msg, sizeof msg, "kolm_patset_create: patterns %u and %u are equal (a set holds distinct patterns)", dup[0],
-                 dup[1]);
-        set_err(msg);
-        return KOLM_EARG;
-    }
-    std::unique_ptr<kolm_patset> ps(new kolm_patset);
-    ps->c = c;
-    ps->info = T.info;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->active = c->stream;  // c->sync() below waits for the uploads
-        auto up = [&](auto*& d, const auto& v) {
-            KOLM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), v.size() * sizeof(v[0])));
-            KOLM_HIP_CHECK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream));
-        };
-        up(ps->d_filter, T.filter), up(ps->d_slots, T.slots), up(ps->d_entries, T.entries), up(ps->d_blob, T.blob);
-        KOLM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ps->d_pcnt), sizeof(u64) * np));
-        c->sync();  // the host tables go out of scope
-        ps->dev = T.view();
-        ps->dev.filter = ps->d_filter, ps->dev.slots = ps->d_slots, ps->dev.entries = ps->d_entries, ps->dev.blob = ps->d_blob;
-        return KOLM_OK;
-    });
-    if (rc) {
-        patset_release(ps.get());
-        return rc;
-    }
-    *out = ps.release();
-    return KOLM_OK;
-}
-
-void kolm_patset_free(kolm_patset* ps) {
-    if (!ps) return;
-    if (ps->c) {
-        std::lock_guard<std::mutex> g(ps->c->mu);
-        (void)hipSetDevice(ps->c->device);
-        patset_release(ps);
-    }
-    delete ps;
-}
-
-int kolm_patset_info(const kolm_patset* ps, kolm_patset_info_t* out) {
-    if (!ps || !out) return KOLM_EARG;
-    *out = kolm_patset_info_t{ps->info.np,   ps->info.K, ps->info.keys,          ps->info.slots,
-                              ps->info.filter_bits, ps->info.L, ps->info.longest_bucket};
-    return KOLM_OK;
-}
-
-int kolm_find_set_device(kolm_ctx* c, const void* d_data, uint64_t n, const kolm_patset* ps, uint64_t max_results,
-                         uint64_t* counts, uint64_t* offs, uint32_t* which, uint64_t cap, uint64_t* nfound, double* ms) {
-    if (ms) *ms = 0.0;
-    if (nfound) *nfound = 0;
-    if (!c || !ps || !nfound) return KOLM_EARG;
-    if (ps->c != c) {
-        set_err("kolm_find_set_device: the pattern set belongs to another context");
-        return KOLM_EARG;
-    }
-    if (n >= (1ull << 31)) {
-        set_err("kolm_find_set_device: the buffer must be smaller than 2^31 bytes");
-        return KOLM_EARG;
-    }
-    if ((n && !d_data) || (cap && (!offs || !which))) return KOLM_EARG;
-    const u32 np = ps->info.np;
-    if (counts)
-        for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    if (n == 0) return KOLM_OK;
-    return guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        c->active = c->stream;
-        findset_zero_counts(c, ps);
-        std::vector<u64> o;
-        std::vector<u32> w;
-        u32 launches = 0;
-        double t = 0.0;
-        u64 more = cap, matches = 0;
-        findset_group(c, ps, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, 0, max_results, matches, o, w, launches, t,
-                      &more);
-        findset_read_counts(c, ps, counts);
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        if (ms) *ms = t;
-        if (more > cap) {
-            *nfound = more;
-            set_err("kolm_find_set_device: result capacity too small");
-            return KOLM_ECAP;
-        }
-        *nfound = o.size();
-        std::copy(o.begin(), o.end(), offs);
-        std::copy(w.begin(), w.end(), which);
-        return KOLM_OK;
-    });
-}
-
-int kolm_reader_find_set(kolm_reader* r, const kolm_patset* ps, uint64_t lo, uint64_t hi, uint64_t max_results,
-                         uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
-    if (stats) *stats = kolm_find_stats{};
-    if (nfound) *nfound = 0;
-    if (!r || !r->c || !ps || !nfound) return KOLM_EARG;
-    // every argument check before the first launch: the set's context, the window, the selected blocks
-    if (ps->c != r->c) {
-        set_err("kolm_reader_find_set: the pattern set and the reader belong to different contexts");
-        return KOLM_EARG;
-    }
-    const u32 np = ps->info.np;
-    RangePlan p;
-    kolm_find_stats st{};
-    st.patterns = np;
-    if (int rc = find_plan("kolm_reader_find_set", r, lo, hi, p, st)) return rc;
-    if (counts)
-        for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    kolm_ctx* c = r->c;
-    std::vector<u64> offs;
-    std::vector<u32> which;
-    std::vector<u64> hc(counts ? np : 0);
-    u64 matches = 0;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
-        if (p.sel.empty()) return KOLM_OK;
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        c->active = c->stream;
-        findset_zero_counts(c, ps);
-        if (int e = find_over_groups(r, p, lo, hi, ps->info.L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
-                findset_group(c, ps, buf, gs.n, gs.lo, gs.shi, gs.start, max_results, matches, offs, which, st.emit_launches,
-                              st.ms_find);
-            }))
-            return e;
-        findset_read_counts(c, ps, counts ? hc.data() : nullptr);
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        return KOLM_OK;
-    });
-    if (rc) {  // no results leave a failed call
-        if (stats) *stats = st;
-        return rc;
-    }
-    if (counts) std::copy(hc.begin(), hc.end(), counts);
-    st.matches = matches;
-    st.returned = offs.size();
-    *nfound = offs.size();
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->fs_offs.swap(offs), r->fs_which.swap(which);
-    }
-    if (stats) *stats = st;
-    return KOLM_OK;
-}
-
-int kolm_reader_find_copy32(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint32_t* which) {
-    if (!r || !r->c) return KOLM_EARG;
-    std::lock_guard<std::mutex> g(r->c->mu);
-    if (first > r->fs_offs.size() || n > r->fs_offs.size() - first) {
-        set_err("kolm_reader_find_copy32: more results than the last find_set holds");
-        return KOLM_EARG;
-    }
-    if (n && !offs) return KOLM_EARG;
-    std::copy(r->fs_offs.begin() + first, r->fs_offs.begin() + first + n, offs);
-    if (which) std::copy(r->fs_which.begin() + first, r->fs_which.begin() + first + n, which);
-    return KOLM_OK;
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int kolm_reader_open(kolm_ctx* c, const uint8_t* container, uint64_t cn, kolm_reader** out) {
-    if (!out) return KOLM_EARG;
-    *out = nullptr;
-    if (!c) c = need_default();
-    if (!c) return KOLM_ENOINIT;
-    if (!container && cn) return KOLM_EARG;
-    u32 fields[4] = {};
-    u64 start = 0;
-    std::vector<u32> methods(65536), lens(65536);
-    std::vector<u64> poff(65537);
-    if (int rc = kolm_toc_read(container, cn, fields, &start, methods.data(), lens.data(), poff.data(), 65536)) return rc;
-    std::unique_ptr<kolm_reader> r(new kolm_reader);
-    r->c = c;
-    r->mode = fields[0], r->size_field = fields[1], r->total = fields[2], r->nb = fields[3];
-    methods.resize(r->nb), lens.resize(r->nb), poff.resize((size_t)r->nb + 1);
-    r->starts.assign((size_t)r->nb + 1, 0);
-    for (u32 i = 0; i < r->nb; ++i) r->starts[i + 1] = r->starts[i] + lens[i];
-    if (r->starts[r->nb] != r->total) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "Length mismatch: got %llu, expect %llu", (unsigned long long)r->starts[r->nb],
-                 (unsigned long long)r->total);
-        set_err(msg);
-        return KOLM_EFORMAT;
-    }
-    for (u32 i = 0; i < r->nb; ++i)
-        if (poff[i + 1] < poff[i]) return KOLM_EFORMAT;
-    r->methods.swap(methods), r->lens.swap(lens), r->poff.swap(poff);
-    r->pbytes = r->nb ? r->poff[r->nb] - r->poff[0] : 0;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        KOLM_HIP_CHECK(hipMalloc((void**)&r->dpay, r->pbytes + 64 + rng::WORD));
-        if (r->pbytes) {
-            const hipError_t e = hipMemcpy(r->dpay, container + start + r->poff[0], r->pbytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(r->dpay);
-                r->dpay = nullptr;
-                KOLM_HIP_CHECK(e);
-            }
-        }
-        return KOLM_OK;
-    });
-    if (rc) return rc;
-    *out = r.release();
-    return KOLM_OK;
-}
-
-int kolm_reader_close(kolm_reader* r) {
-    if (!r) return KOLM_EARG;
-    kolm_ctx* c = r->c;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        if (r->dpay) KOLM_HIP_CHECK(hipFree(r->dpay));
-        return KOLM_OK;
-    });
-    delete r;
-    return rc;
-}
-
-int kolm_reader_info(kolm_reader* r, uint64_t* info, uint32_t* methods, uint32_t* orig_lens, uint32_t cap) {
-    if (!r || !info) return KOLM_EARG;
-    info[0] = r->mode, info[1] = r->size_field, info[2] = r->total, info[3] = r->nb, info[4] = r->pbytes;
-    if ((methods || orig_lens) && cap < r->nb) {
-        set_err("kolm_reader_info: capacity too small");
-        return KOLM_ECAP;
-    }
-    if (methods) std::copy(r->methods.begin(), r->methods.end(), methods);
-    if (orig_lens) std::copy(r->lens.begin(), r->lens.end(), orig_lens);
-    return KOLM_OK;
-}
-
-int kolm_reader_read(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges, uint8_t* out,
-                     uint64_t out_cap, kolm_read_stats* stats) {
-    return reader_read(r, offs, lens, nranges, out, nullptr, out_cap, stats);
-}
-
-int kolm_reader_read_device(kolm_reader* r, const uint64_t* offs, const uint64_t* lens, uint32_t nranges, void* d_out,
-                            uint64_t out_cap, kolm_read_stats* stats) {
-    if (!d_out && nranges) {
-        u64 want = 0;
-        for (u32 i = 0; offs && lens && i < nranges; ++i) want += lens[i];
-        if (want) return KOLM_EARG;
-    }
-    return reader_read(r, offs, lens, nranges, nullptr, d_out, out_cap, stats);
-}
-
 // ---- checksums (crc_core.h, k_crc.hip; the helpers stand with the verify step above) ----
 uint32_t kolm_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc::combine(crc_a, crc_b, len_b); }
 
@@ -4738,216 +3418,30 @@ int kolm_check_container(const uint8_t* container, uint64_t cn, const uint32_t* 
     if (!container && cn) return KOLM_EARG;
     kolm_check_report r{};
     if (rep) *rep = r;
-    u32 fields[4] = {};
-    u64 start = 0;
-    std::vector<u32> methods(65536), lens(65536);
-    std::vector<u64> poff(65537);
-    if (int rc = kolm_toc_read(container, cn, fields, &start, methods.data(), lens.data(), poff.data(), 65536)) return rc;
-    const u32 nb = fields[3];
-    if (got && cap < nb) {
+    Toc t;
+    if (int rc = toc_load(container, cn, t)) return rc;
+    const u32 nb = t.nb;
+    if (got && cap < nb) {  // this entry reports a short `got` before lengths that do not add up
         set_err("got capacity too small");
         return KOLM_ECAP;
     }
-    u64 sum = 0;
-    for (u32 i = 0; i < nb; ++i) sum += lens[i];
-    if (sum != fields[2]) {  // as kolm_reader_open: the TOC's lengths do not add up to total_len
-        char msg[96];
-        snprintf(msg, sizeof msg, "Length mismatch: got %llu, expect %llu", (unsigned long long)sum,
-                 (unsigned long long)fields[2]);
-        set_err(msg);
-        return KOLM_EFORMAT;
-    }
+    if (int rc = toc_check_length(t)) return rc;
     if (nb == 0) return KOLM_OK;
     int rc = guarded([&] {
         std::lock_guard<std::mutex> g(c->mu);
         KOLM_HIP_CHECK(hipSetDevice(c->device));
         c->timing_reset();
-        const u64 ptotal = poff[nb] - poff[0];
+        const u64 ptotal = t.poff[nb] - t.poff[0];
         u8* dpay = c->get<u8>("vfy_pay", ptotal + 64);
         if (ptotal)
-            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, container + start + poff[0], ptotal, hipMemcpyHostToDevice, c->stream));
-        return check_run(c, lens.data(), nb, dpay, poff.data(), methods.data(), expect, got, r);
+            KOLM_HIP_CHECK(hipMemcpyAsync(dpay, container + t.start + t.poff[0], ptotal, hipMemcpyHostToDevice, c->stream));
+        return check_run(c, t.lens.data(), nb, dpay, t.poff.data(), t.methods.data(), expect, got, r);
     });
     if (rep) *rep = r;
     return rc;
 }
 
-int kolm_reader_set_checksums(kolm_reader* r, const uint32_t* crc_in, uint32_t nblocks) {
-    if (!r || !r->c) return KOLM_EARG;
-    std::lock_guard<std::mutex> g(r->c->mu);
-    if (!crc_in) {
-        r->crcs.clear();
-        return KOLM_OK;
-    }
-    if (nblocks != r->nb) {
-        set_err("kolm_reader_set_checksums: the block count differs from the container's");
-        return KOLM_EARG;
-    }
-    r->crcs.assign(crc_in, crc_in + nblocks);
-    return KOLM_OK;
-}
-
-}  // extern "C"
-
-// ---- line index: lines of a container on the device (lines_core.h, k_lines.hip, kolm_lines.cpp) ----
-namespace {
-
-// every selected block must be one the device decodes (as reads and searches check)
-int lines_check_blocks(kolm_reader* r, const RangePlan& p, kolm_lines_stats& st) {
-    st.blocks_decoded = (u32)p.sel.size();
-    st.groups = (u32)p.group_first.size() - 1;
-    for (u32 b : p.sel) {
-        const u32 m = r->methods[b];
-        if (m >= 32 || !((KOLM_DECODE_MASK >> m) & 1u) || (m == KOLM_M_V2NEW && r->lens[b] >= (1u << 28)) ||
-            r->lens[b] >= (1u << 31)) {
-            char msg[128];
-            snprintf(msg, sizeof msg, "block %u (method %u, %u bytes) is not decoded on the device", b, m, r->lens[b]);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        st.bytes_decoded += r->lens[b];
-    }
-    return KOLM_OK;
-}
-
-// Group g of the plan decoded into the "rd_dec" scratch (its blocks back to back; w.gl their
-// lengths), as a read decodes it: payload runs, compaction, decode_batch, then the status and
-// checksum checks before anything else looks at the bytes.  The caller holds the context's lock.
-struct GroupDec {
-    std::vector<u32> gm, gl, status, scan, words;
-    std::vector<u64> gp;
-    std::vector<rng::Seg> runs;
-};
-int lines_decode_group(kolm_reader* r, const RangePlan& p, u32 g, GroupDec& w, u8*& dec, u64& tot, kolm_lines_stats& st) {
-    kolm_ctx* c = r->c;
-    const u32 i0 = p.group_first[g], i1 = p.group_first[g + 1], n = i1 - i0;
-    w.gm.resize(n), w.gl.resize(n), w.gp.assign((size_t)n + 1, 0);
-    w.runs.clear();
-    tot = 0;
-    for (u32 i = i0; i < i1; ++i) {
-        const u32 b = p.sel[i];
-        w.gm[i - i0] = r->methods[b];
-        w.gl[i - i0] = r->lens[b];
-        tot += r->lens[b];
-        const u64 plen = r->poff[b + 1] - r->poff[b];
-        if (i == i0 || b != p.sel[i - 1] + 1) w.runs.push_back(rng::Seg{r->poff[b] - r->poff[0], w.gp[i - i0], 0});
-        w.runs.back().len += plen;
-        w.gp[i - i0 + 1] = w.gp[i - i0] + plen;
-    }
-    const u8* pay = r->dpay + w.runs[0].src;
-    if (w.runs.size() > 1) {  // as reads do: several payload runs are gathered first
-        u8* stage = c->get<u8>("rd_pay", w.gp[n] + 64);
-        gather_segments(c, "rd_c", r->dpay, stage, w.runs.data(), (u32)w.runs.size(), w.scan, c->ev[4], c->ev[5]);
-        pay = stage;
-    }
-    dec = c->get<u8>("rd_dec", tot + 64 + rng::WORD);
-    double ms = 0.0;
-    if (int e = decode_batch(c, pay, w.gp.data(), w.gm.data(), w.gl.data(), n, tot, dec, &ms, &w.status)) return e;
-    st.ms_decode += ms;
-    for (u32 i = 0; i < n; ++i)
-        if (w.status[i]) {
-            char msg[128];
-            snprintf(msg, sizeof msg, "block %u (method %u): %s", p.sel[i0 + i], w.gm[i],
-                     w.status[i] == DEC_ELEN ? "decoded length mismatch" : "malformed payload");
-            set_err(msg);
-            return KOLM_EARG;
-        }
-    if (!r->crcs.empty()) {
-        w.words.resize(n);
-        crc_blocks_at(c, dec, w.gl.data(), n, w.words.data());
-        for (u32 i = 0; i < n; ++i) {
-            const u32 b = p.sel[i0 + i];
-            if (w.words[i] != r->crcs[b]) {
-                checksum_message(b, w.gm[i], r->crcs[b], w.words[i]);
-                return KOLM_ECHECKSUM;
-            }
-        }
-    }
-    return KOLM_OK;
-}
-
-void lines_message(u32 block, u32 expected, u32 got) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "line index: block %u: expected %u delimiters, got %u", block, expected, got);
-    set_err(msg);
-}
-
-// The plan whose selected blocks are `blocks` (ascending, distinct, none empty), grouped as a
-// read's blocks are: one 1-byte range at each block's start.
-int lines_plan(kolm_reader* r, const std::vector<u32>& blocks, RangePlan& p) {
-    std::vector<u64> offs(blocks.size()), lens(blocks.size(), 1);
-    for (size_t i = 0; i < blocks.size(); ++i) offs[i] = r->starts[blocks[i]];
-    return range_plan(r->lens.data(), r->starts.data(), r->nb, offs.data(), lens.data(), (u32)blocks.size(), 0, p);
-}
-
-// The queries q (sorted by block; q[i].block = the container's block, never an empty one) answered
-// group by group: res[i].  Each group's real counts are compared with the attached index first.
-int lines_run(kolm_reader* r, std::vector<lin::Query>& q, std::vector<u32>& res, kolm_lines_stats& st) {
-    st.queries = (u32)q.size();
-    res.assign(q.size(), 0);
-    if (q.empty()) return KOLM_OK;
-    std::vector<u32> blocks, cb(q.size());  // cb: the queries' container block numbers
-    for (size_t i = 0; i < q.size(); ++i) {
-        cb[i] = q[i].block;
-        if (blocks.empty() || blocks.back() != cb[i]) blocks.push_back(cb[i]);
-    }
-    RangePlan p;
-    if (int rc = lines_plan(r, blocks, p)) return rc;
-    if (int rc = lines_check_blocks(r, p, st)) return rc;
-    kolm_ctx* c = r->c;
-    return guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        c->active = c->stream;
-        GroupDec w;
-        std::vector<u32> hb, cnt;
-        size_t q0 = 0;
-        for (u32 gi = 0; gi + 1 < p.group_first.size(); ++gi) {
-            const u32 i0 = p.group_first[gi], i1 = p.group_first[gi + 1], n = i1 - i0;
-            u8* dec = nullptr;
-            u64 tot = 0;
-            if (int e = lines_decode_group(r, p, gi, w, dec, tot, st)) return e;
-            // the group's queries: q[q0, q1), their blocks renumbered to the group's slots
-            size_t q1 = q0;
-            u32 slot = 0;
-            while (q1 < q.size() && cb[q1] <= p.sel[i1 - 1]) {
-                while (p.sel[i0 + slot] != cb[q1]) ++slot;
-                q[q1++].block = slot;
-            }
-            hb.assign((size_t)n + 1, 0);
-            for (u32 i = 0; i < n; ++i) hb[i + 1] = hb[i] + w.gl[i];
-            cnt.resize(n);
-            lines_prepare(c, dec, tot, 0, hb.data(), n, r->ldelim, true, q.data() + q0, (u32)(q1 - q0));
-            lines_launch(c, c->stream);
-            st.ms_lines += lines_collect(c, cnt.data(), res.data() + q0);
-            for (u32 i = 0; i < n; ++i)
-                if (cnt[i] != r->lcounts[p.sel[i0 + i]]) {
-                    lines_message(p.sel[i0 + i], r->lcounts[p.sel[i0 + i]], cnt[i]);
-                    return KOLM_ELINES;
-                }
-            for (size_t i = q0; i < q1; ++i)
-                if (res[i] == lin::NONE) {
-                    lines_message(cb[i], r->lcounts[cb[i]], cnt[q[i].block]);
-                    return KOLM_ELINES;
-                }
-            q0 = q1;
-        }
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        return KOLM_OK;
-    });
-}
-
-int lines_need_index(const char* who, kolm_reader* r) {
-    if (r->has_lines) return KOLM_OK;
-    set_err(std::string(who) + ": no line index is attached (kolm_reader_set_lines / kolm_reader_index_lines)");
-    return KOLM_EARG;
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- line index: delimiter counts of resident blocks (the pass stands with the checksum helpers above) ----
 int kolm_delim_count_device(kolm_ctx* c, const void* d_data, const uint64_t* h_bounds, uint32_t nblocks, uint32_t delim,
                             uint32_t* counts, double* ms) {
     if (!c) return KOLM_EARG;
@@ -5014,165 +3508,6 @@ int kolm_delim_count_pieces_device(kolm_ctx* c, const void* d_data, const uint64
         if (ms) *ms = t;
         return KOLM_OK;
     });
-}
-
-int kolm_reader_set_lines(kolm_reader* r, uint32_t delim, const uint32_t* counts, uint32_t nblocks) {
-    if (!r || !r->c) return KOLM_EARG;
-    std::lock_guard<std::mutex> g(r->c->mu);
-    if (!counts) {
-        r->has_lines = false;
-        r->lcounts.clear();
-        return KOLM_OK;
-    }
-    if (delim > 0xFFu) {
-        set_err("kolm_reader_set_lines: the delimiter is one byte value");
-        return KOLM_EARG;
-    }
-    if (nblocks != r->nb) {
-        set_err("kolm_reader_set_lines: the block count differs from the container's");
-        return KOLM_EARG;
-    }
-    r->lcounts.assign(counts, counts + nblocks);
-    r->ldelim = delim;
-    r->has_lines = true;
-    return KOLM_OK;
-}
-
-int kolm_reader_index_lines(kolm_reader* r, uint32_t delim, uint32_t* counts, uint32_t cap, kolm_lines_stats* stats) {
-    if (stats) *stats = kolm_lines_stats{};
-    if (!r || !r->c) return KOLM_EARG;
-    if (delim > 0xFFu) {
-        set_err("kolm_reader_index_lines: the delimiter is one byte value");
-        return KOLM_EARG;
-    }
-    if (counts && cap < r->nb) {
-        set_err("kolm_reader_index_lines: capacity too small");
-        return KOLM_ECAP;
-    }
-    kolm_lines_stats st{};
-    RangePlan p;
-    const u64 lo = 0, len = r->total;
-    if (int rc = range_plan(r->lens.data(), r->starts.data(), r->nb, &lo, &len, 1, 0, p)) return rc;
-    if (int rc = lines_check_blocks(r, p, st)) return rc;
-    std::vector<u32> all(r->nb, 0);
-    kolm_ctx* c = r->c;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (p.sel.empty()) return KOLM_OK;
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        c->active = c->stream;
-        GroupDec w;
-        std::vector<u32> hb, cnt;
-        for (u32 gi = 0; gi + 1 < p.group_first.size(); ++gi) {
-            const u32 i0 = p.group_first[gi], n = p.group_first[gi + 1] - i0;
-            u8* dec = nullptr;
-            u64 tot = 0;
-            if (int e = lines_decode_group(r, p, gi, w, dec, tot, st)) return e;
-            hb.assign((size_t)n + 1, 0);
-            for (u32 i = 0; i < n; ++i) hb[i + 1] = hb[i] + w.gl[i];
-            cnt.resize(n);
-            lines_prepare(c, dec, tot, 0, hb.data(), n, delim, false);
-            lines_launch(c, c->stream);
-            st.ms_lines += lines_collect(c, cnt.data());
-            for (u32 i = 0; i < n; ++i) all[p.sel[i0 + i]] = cnt[i];
-        }
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        return KOLM_OK;
-    });
-    if (stats) *stats = st;
-    if (rc) return rc;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->lcounts = all;
-        r->ldelim = delim;
-        r->has_lines = true;
-    }
-    if (counts) std::copy(all.begin(), all.end(), counts);
-    return KOLM_OK;
-}
-
-int kolm_reader_line_spans(kolm_reader* r, const uint64_t* lines, uint32_t n, uint64_t* starts, uint64_t* ends,
-                           kolm_lines_stats* stats) {
-    if (stats) *stats = kolm_lines_stats{};
-    if (!r || !r->c || (n && (!lines || !starts || !ends))) return KOLM_EARG;
-    if (int rc = lines_need_index("kolm_reader_line_spans", r)) return rc;
-    // every argument check before the first launch: the lines, the selected blocks
-    std::vector<u64> prefix;
-    lines_prefix(r->lcounts.data(), r->nb, prefix);
-    const u64 D = prefix[r->nb];
-    std::vector<u64> need;  // the delimiters whose positions the spans are made of, each once
-    for (u32 i = 0; i < n; ++i) {
-        if (lines[i] > D) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "kolm_reader_line_spans: entry %u: line %llu of %llu", i, (unsigned long long)lines[i],
-                     (unsigned long long)(D + 1));
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        if (lines[i] > 0) need.push_back(lines[i] - 1);
-        if (lines[i] < D) need.push_back(lines[i]);
-    }
-    std::sort(need.begin(), need.end());
-    need.erase(std::unique(need.begin(), need.end()), need.end());
-    std::vector<lin::Query> q(need.size());  // ascending delimiter numbers: sorted by block
-    for (size_t i = 0; i < need.size(); ++i) {
-        const u32 b = lines_block_of(prefix, need[i]);
-        q[i] = lin::Query{b, (u32)(need[i] - prefix[b]), lin::OP_SELECT};
-    }
-    const std::vector<lin::Query> asked = q;
-    kolm_lines_stats st{};
-    std::vector<u32> res;
-    const int rc = lines_run(r, q, res, st);
-    if (stats) *stats = st;
-    if (rc) return rc;  // no results leave a failed call
-    auto pos = [&](u64 k) {
-        const size_t i = (size_t)(std::lower_bound(need.begin(), need.end(), k) - need.begin());
-        return r->starts[asked[i].block] + res[i];
-    };
-    for (u32 i = 0; i < n; ++i) {
-        starts[i] = lines[i] ? pos(lines[i] - 1) + 1 : 0;
-        ends[i] = lines[i] < D ? pos(lines[i]) : r->total;
-    }
-    return KOLM_OK;
-}
-
-int kolm_reader_line_of(kolm_reader* r, const uint64_t* offs, uint32_t n, uint64_t* lines, kolm_lines_stats* stats) {
-    if (stats) *stats = kolm_lines_stats{};
-    if (!r || !r->c || (n && (!offs || !lines))) return KOLM_EARG;
-    if (int rc = lines_need_index("kolm_reader_line_of", r)) return rc;
-    std::vector<u64> prefix;
-    lines_prefix(r->lcounts.data(), r->nb, prefix);
-    // (block, offset in it) of every offset that needs a decode, each once, sorted by block
-    std::vector<std::pair<u32, u32>> at(n), need;
-    for (u32 i = 0; i < n; ++i) {
-        if (offs[i] > r->total) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "kolm_reader_line_of: entry %u: offset %llu is not inside the container's %llu bytes", i,
-                     (unsigned long long)offs[i], (unsigned long long)r->total);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        const u32 b = offs[i] == r->total
-                          ? r->nb
-                          : (u32)(std::upper_bound(r->starts.begin(), r->starts.end(), offs[i]) - r->starts.begin()) - 1;
-        at[i] = {b, (u32)(offs[i] - r->starts[b])};
-        if (at[i].second) need.push_back(at[i]);  // a block's start, the stream's end: the prefix sum alone
-    }
-    std::sort(need.begin(), need.end());
-    need.erase(std::unique(need.begin(), need.end()), need.end());
-    std::vector<lin::Query> q(need.size());
-    for (size_t i = 0; i < need.size(); ++i) q[i] = lin::Query{need[i].first, need[i].second, lin::OP_RANK};
-    kolm_lines_stats st{};
-    std::vector<u32> res;
-    const int rc = lines_run(r, q, res, st);
-    if (stats) *stats = st;
-    if (rc) return rc;
-    for (u32 i = 0; i < n; ++i) {
-        lines[i] = prefix[at[i].first];
-        if (at[i].second) lines[i] += res[(size_t)(std::lower_bound(need.begin(), need.end(), at[i]) - need.begin())];
-    }
-    return KOLM_OK;
 }
 
 int kolm_ctx_set_lines(kolm_ctx* c, int enable, uint32_t delim) {

@@ -1,4 +1,4 @@
-"""The line index on the device (kolmogorovlike-datacompressor_amd/csrc/k_lines.hip, kolm_api.cpp):
+"""The line index on the device (kolmogorovlike-datacompressor_amd/csrc/k_lines.hip, kolm_api.cpp, kolm_reader.cpp):
 k_delim_count against bytes.count and the CPU emulation (tools/lines_emu.cpp), and a Reader's
 line_count / line_spans / line_of / read_lines / grep over containers made here against
 data.split, a host list of the delimiter positions with bisect, and repeated bytes.find.  No

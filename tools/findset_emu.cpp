@@ -69,7 +69,7 @@ struct FsEmu {
     }
 };
 
-// One group as the host runs it (findset_group of kolm_api.cpp).
+// One group as the host runs it (findset_group and emit_matches of kolm_reader.cpp).
 u64 fs_group(const u8* buf, u32 n, u32 lo, u32 shi, const fst::Set& S, u64 base, u64 stage_bytes, u64 limit, u64* pcnt,
              std::vector<u64>& offs, std::vector<u32>& which, u32* launches) {
     FsEmu e{Ld{buf, n}, lo, shi, S};

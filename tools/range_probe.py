@@ -51,6 +51,8 @@ def main():
         m = int(rng.integers(256, 4097))
         small.append((int(rng.integers(0, n - m + 1)), m))
     small_bytes = sum(m for _, m in small)
+    if small_bytes > n:  # the packed small ranges land in the n + 64 bytes of `out`
+        sys.exit(f"--blocks {args.blocks}: the 65536 small ranges hold {small_bytes} bytes, more than the {n} of the data")
     thousand = small[:1000]
     big = n - 64
     out = _lib.DeviceBuffer(ctx, n + 64)
