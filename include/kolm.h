@@ -141,7 +141,9 @@ int kolm_bbwt_forward(const uint8_t* in, size_t n, uint8_t* out);
 /* out: n bytes (MTF indices 0..255). */
 int kolm_mtf_encode(const uint8_t* in, size_t n, uint8_t* out);
 /* Rice code of the byte sequence, parameter k in [0, 15]; worst case
- * n*(255/2^k + 1 + k)/8 + 1 bytes. */
+ * n*(255/2^k + 1 + k)/8 + 1 bytes.  A code of 2^32 bits or more (possible from n = 2^24
+ * at k = 0) is refused with KOLM_ERANGE, *out_len = 0 and nothing written to out; the same
+ * holds for kolm_bbwt_mtf_rice with flags 0. */
 int kolm_rice_encode(const uint8_t* in, size_t n, int k, uint8_t* out, size_t cap, size_t* out_len);
 /* LZ77 stream (worst case 2n bytes). */
 int kolm_lz77_encode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len);

@@ -459,12 +459,20 @@ void launch_emit_simple(const EmitArgs& e, hipStream_t s) {
     k_emit_simple<<<nt, WG, 0, s>>>(tg, e.text, e.method, e.off, e.tile_tmp + nt, e.arena);
 }
 
-static void rice_emit_common(const Geom& geo, const u8* seq, const u32* method, int force_flag, int k,
-                             const u64* off, u8* arena, u32* tile_tmp, hipStream_t s) {
+// per-tile bit counts into tile_tmp[0, nt) and their per-block exclusive sums into tile_tmp[nt, 2 nt)
+static u32 rice_count_tiles(const Geom& geo, const u8* seq, const u32* method, int force_flag, int k,
+                            u32* tile_tmp, hipStream_t s) {
     TileG tg{geo, cdiv32(geo.bs, TILE)};
     const u32 nt = tg.tpb * geo.nb;
     k_rice_count<<<nt, WG, 0, s>>>(tg, seq, method, force_flag, k, tile_tmp);
     k_tiles_excl_add<<<geo.nb, WG, 0, s>>>(tile_tmp, tile_tmp + nt, tg.tpb);
+    return nt;
+}
+
+static void rice_emit_tiles(const Geom& geo, const u8* seq, const u32* method, int force_flag, int k,
+                            const u64* off, u8* arena, u32* tile_tmp, hipStream_t s) {
+    TileG tg{geo, cdiv32(geo.bs, TILE)};
+    const u32 nt = tg.tpb * geo.nb;
     const u32 maxbits = TILE * ((255u >> k) + 1 + k) + 64;
     const u32 words = (maxbits + 31) / 32 + 2;
     if (words * 4 > 65536)
@@ -473,29 +481,43 @@ static void rice_emit_common(const Geom& geo, const u8* seq, const u32* method, 
     k_rice_emit<<<nt, WG, words * 4, s>>>(tg, seq, method, force_flag, k, off, tile_tmp + nt, arena, words);
 }
 
+static void rice_emit_common(const Geom& geo, const u8* seq, const u32* method, int force_flag, int k,
+                             const u64* off, u8* arena, u32* tile_tmp, hipStream_t s) {
+    rice_count_tiles(geo, seq, method, force_flag, k, tile_tmp, s);
+    rice_emit_tiles(geo, seq, method, force_flag, k, off, arena, tile_tmp, s);
+}
+
 void launch_emit_rice(const EmitArgs& e, hipStream_t s) {
     if (!e.geo.N) return;
     rice_emit_common(e.geo, e.mtf, e.method, -1, e.rice_k, e.off, e.arena, e.tile_tmp, s);
 }
 
-// Rice of a plain byte sequence (kolm_rice_encode): one block, flag 0.  out must be zeroed;
-// *out_size receives the byte size.
-__global__ void k_rice_total(const u32* toff, const u32* tsum, u32 nt, u32* out_size) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const u64 bits = (u64)toff[nt - 1] + tsum[nt - 1];
-        *out_size = (u32)((bits + 7) / 8);
-    }
+// Rice of a plain byte sequence (kolm_rice_encode): one block, flag 0, in two steps so that the
+// host sees the code's length before anything is emitted.  The tiles' bit offsets (k_tiles_excl_add)
+// and k_rice_emit's tile start are 32-bit: a code of 2^32 bits or more must not be emitted.
+__global__ __launch_bounds__(WG) void k_rice_total(const u32* tsum, u32 nt, u64* total_bits) {
+    __shared__ u64 sh[WG / 64];
+    u64 v = 0;
+    for (u32 i = threadIdx.x; i < nt; i += WG) v += tsum[i];
+    v = wg_sum<u64>(v, sh);
+    if (threadIdx.x == 0) *total_bits = v;
 }
 
-void launch_rice_only(const Geom& geo, const u8* in, int k, u8* out, u32* tile_tmp, u32* tile_tmp2,
-                      u32* out_size, hipStream_t s) {
+// the count pass: per-tile counts and offsets in tile_tmp, the code's length in bits (64-bit sum of
+// the tile counts) in *total_bits
+void launch_rice_only_count(const Geom& geo, const u8* in, int k, u32* tile_tmp, u64* total_bits, hipStream_t s) {
+    if (!geo.N) return;
+    const u32 nt = rice_count_tiles(geo, in, nullptr, 0, k, tile_tmp, s);
+    k_rice_total<<<1, WG, 0, s>>>(tile_tmp, nt, total_bits);
+}
+
+// the emission after launch_rice_only_count, for a code under 2^32 bits.  out must be zeroed.
+void launch_rice_only_emit(const Geom& geo, const u8* in, int k, u8* out, u32* tile_tmp, u32* tile_tmp2,
+                           hipStream_t s) {
     if (!geo.N) return;
     // offsets: single block at byte 0 (tile_tmp2 holds a zero u64)
     KOLM_HIP_CHECK(hipMemsetAsync(tile_tmp2, 0, sizeof(u64), s));
-    rice_emit_common(geo, in, nullptr, 0, k, reinterpret_cast<const u64*>(tile_tmp2), out, tile_tmp, s);
-    TileG tg{geo, cdiv32(geo.bs, TILE)};
-    const u32 nt = tg.tpb * geo.nb;
-    k_rice_total<<<1, 64, 0, s>>>(tile_tmp + nt, tile_tmp, nt, out_size);
+    rice_emit_tiles(geo, in, nullptr, 0, k, reinterpret_cast<const u64*>(tile_tmp2), out, tile_tmp, s);
 }
 
 }  // namespace kolm

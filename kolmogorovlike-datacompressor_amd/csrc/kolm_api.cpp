@@ -3582,24 +3582,32 @@ int kolm_mtf_encode(const uint8_t* in, size_t n, uint8_t* out) {
 
 static int rice_common(kolm_ctx* c, const Geom& geo, const u8* d_seq, int k, uint8_t* out, size_t cap,
                        size_t* out_len) {
-    const u64 n = geo.N;
-    const u64 worst = (n * ((255u >> k) + 1 + k) + 7) / 8 + 64;
-    u8* dout = c->get<u8>("rice_out", worst + 64);
-    KOLM_HIP_CHECK(hipMemsetAsync(dout, 0, worst + 64, c->stream));
     const u64 ntiles = (u64)((geo.bs + TILE - 1) / TILE) * geo.nb + 16;
     u32* t1 = c->get<u32>("tile_tmp", 2 * ntiles + 16);
     u32* t2 = c->get<u32>("tile_tmp2", 2 * ntiles + 2 * geo.nb + 16);
-    u32* cnt = c->get<u32>("counters", C_N);
-    launch_rice_only(geo, d_seq, k, dout, t1, t2, cnt + C_RICE, c->stream);
-    KOLM_HIP_CHECK(hipMemcpyAsync(c->h_cnt, cnt, sizeof(u32) * C_N, hipMemcpyDeviceToHost, c->stream));
+    // the count pass first: the emission keeps a block's bit offsets in 32 bits, so a code of 2^32
+    // bits or more (reachable from 16 MiB at k = 0) is refused here, before anything is written
+    u64* d_bits = reinterpret_cast<u64*>(t2) + 1;
+    launch_rice_only_count(geo, d_seq, k, t1, d_bits, c->stream);
+    u64 bits = 0;
+    KOLM_HIP_CHECK(hipMemcpyAsync(&bits, d_bits, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     c->sync();
-    const u32 sz = c->h_cnt[C_RICE];
+    if (bits >= (1ull << 32)) {
+        if (out_len) *out_len = 0;
+        set_err("rice code of " + std::to_string(bits) + " bits: a block's code must stay under 2^32 bits");
+        return KOLM_ERANGE;
+    }
+    const u64 sz = (bits + 7) / 8;
     if (out_len) *out_len = sz;
     if (sz > cap) {
         set_err("rice output capacity too small");
         return KOLM_ECAP;
     }
     if (sz) {
+        // (the tiles' last words are stored whole: up to 3 bytes past sz)
+        u8* dout = c->get<u8>("rice_out", sz + 64);
+        KOLM_HIP_CHECK(hipMemsetAsync(dout, 0, sz + 64, c->stream));
+        launch_rice_only_emit(geo, d_seq, k, dout, t1, t2, c->stream);
         KOLM_HIP_CHECK(hipMemcpyAsync(out, dout, sz, hipMemcpyDeviceToHost, c->stream));
         c->sync();
     }

@@ -433,8 +433,9 @@ void launch_mdl(const EmitArgs& e, const u32* lz_sizes, const u32* rp_result, co
                 hipStream_t s);
 void launch_emit_simple(const EmitArgs& e, hipStream_t s);
 void launch_emit_rice(const EmitArgs& e, hipStream_t s);
-void launch_rice_only(const Geom& geo, const u8* in, int k, u8* out, u32* tile_tmp, u32* tile_tmp2,
-                      u32* out_size, hipStream_t s);
+void launch_rice_only_count(const Geom& geo, const u8* in, int k, u32* tile_tmp, u64* total_bits, hipStream_t s);
+void launch_rice_only_emit(const Geom& geo, const u8* in, int k, u8* out, u32* tile_tmp, u32* tile_tmp2,
+                           hipStream_t s);
 
 // ---- k_v2.hip: candidate 10 (v2_new, opt-in: the reference raises NameError) ----
 constexpr u32 V2_META = 11;  // per-block plane decisions (k_v2_size)

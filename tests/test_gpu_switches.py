@@ -4,7 +4,8 @@ the hot-path candidates with the switch set and compares every block's sizes and
 with the oracle (PY:351-423 BBWT order, PY:460 MTF, PY:1413 Rice, PY:2350-2369 MDL).
 
   KOLM_MTF_WAVE=0   the per-thread MTF replay (and its SWAR Rice sums) on batches of few blocks,
-                    with chunks of 128..512 bytes and ragged block ends
+                    with ragged block ends; mtf_chunk_bytes gives all four inputs chunks of 128 bytes
+                    (256, 512 and 1024: tests/test_gpu_entropy_routes.py)
   KOLM_MTF_WAVE=1   the position-parallel MTF replay on a batch of 64 blocks or more
   KOLM_PREVC_IDX=1  k_prevc on the index stream below 16 blocks (with 16+ blocks: the early BBWT
                     gather from doubling round 3 on the third stream)
