@@ -484,6 +484,32 @@ int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_of
 /* Results [first, first + n) of the reader's last find to offs / which (which optional). */
 int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint8_t* which);
 
+/* ---- class patterns: ignore case, wildcards and byte sets ------------------------------------- */
+/* A class pattern is a sequence of 1..KOLM_FIND_MAX_LEN byte classes, each a subset of 0..255
+ * passed as a 32-byte bitmap (bit b & 7 of byte b >> 3 is byte value b); pattern i takes the
+ * bitmaps [pat_off[i], pat_off[i + 1]) of `bitmaps`.  (o, i) is a match iff lo <= o,
+ * o + len_i <= hi and data[o + j] is in class j of pattern i for every j; a pattern that holds an
+ * empty class has no match.  Counting, order, max_results, the exact totals and the independence
+ * of KOLM_READ_BYTES / KOLM_FIND_STAGE are those of the search above, as are the tile geometry, the
+ * scan, the staged emit, the hold-back between groups and the checksum rule.
+ * The library classifies and deduplicates the classes (csrc/findcls_core.h): a class equal to
+ * {b : (b & mask) == value} (a single byte, every byte, an ASCII case pair, [0-7] ...) counts against
+ * no limit; of all others, the table classes, a call holds at most KOLM_FIND_MAX_TABLE_CLASSES
+ * distinct ones.  k_findcls_count / k_findcls_emit (k_findcls.hip) filter every position with one
+ * masked 64-bit compare on the first 8 classes and look at the table and the later positions
+ * only for candidates.
+ * KOLM_EARG before any launch, the message naming the pattern: np = 0 or np > 16, a pattern of 0
+ * or more than 256 positions, and the position at which a 65th distinct table class appears. */
+#define KOLM_FIND_MAX_TABLE_CLASSES 64
+/* kolm_find_device for class patterns (KOLM_ECAP included). */
+int kolm_find_classes_device(kolm_ctx* ctx, const void* d_data, uint64_t n, const uint8_t* bitmaps,
+                             const uint32_t* pat_off, uint32_t np, uint64_t max_results, uint64_t* counts, uint64_t* offs,
+                             uint8_t* which, uint64_t cap, uint64_t* nfound, double* ms);
+/* kolm_reader_find for class patterns: the result stays in the reader until its next find of any
+ * kind and is copied out by kolm_reader_find_copy. */
+int kolm_reader_find_classes(kolm_reader* r, const uint8_t* bitmaps, const uint32_t* pat_off, uint32_t np, uint64_t lo,
+                             uint64_t hi, uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats);
+
 /* ---- pattern sets: up to 65 536 patterns in one pass ----------------------------------------- */
 /* A set holds np patterns (1..KOLM_FIND_SET_MAX_PATTERNS) of 1..KOLM_FIND_MAX_LEN bytes each,
  * pairwise distinct: two equal patterns are refused with KOLM_EARG, the message naming both

@@ -729,6 +729,15 @@ void launch_findset_emit(const u8* buf, u32 n, u32 lo, u32 shi, const fst::Set& 
                          uint2* out, u32 cap, hipStream_t s);
 }  // namespace kolm
 
+// ---- k_findcls.hip: search of a resident buffer for class patterns (findcls_core.h) ----
+#include "findcls_core.h"
+namespace kolm {
+// as launch_find_count / launch_find_emit (launch_find_scan between them), P the call's class patterns
+void launch_findcls_count(const u8* buf, u32 n, u32 lo, u32 shi, const fcl::Pats* P, u32 np, u32* cnt, hipStream_t s);
+void launch_findcls_emit(const u8* buf, u32 n, u32 lo, u32 shi, const fcl::Pats* P, u32 np, u32 t0, u32 t1,
+                         const u64* tscan, u32* out_pos, u8* out_which, u32 cap, hipStream_t s);
+}  // namespace kolm
+
 #define KOLM_HIP_CHECK(x)                                              \
     do {                                                               \
         hipError_t e_ = (x);                                           \

@@ -425,6 +425,101 @@ int find_over_groups(kolm_reader* r, const RangePlan& p, u64 lo, u64 hi, u32 L, 
     return KOLM_OK;
 }
 
+// ---- class patterns (findcls_core.h, k_findcls.hip) ----
+
+// np class patterns, pattern i = the 32-byte bitmaps [pat_off[i], pat_off[i + 1]); L = the longest.
+// Classifies and deduplicates the classes into hp (no launch yet).
+int findcls_check_pats(const char* who, const uint8_t* bitmaps, const uint32_t* pat_off, u32 np, u32* L, fcl::Pats& hp) {
+    char msg[200];
+    if (np < 1 || np > KOLM_FIND_MAX_PATTERNS) {
+        snprintf(msg, sizeof msg, "%s: %u patterns (1..%u are allowed)", who, np, (u32)KOLM_FIND_MAX_PATTERNS);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    if (!bitmaps || !pat_off) return KOLM_EARG;
+    *L = 0;
+    for (u32 i = 0; i < np; ++i) {
+        if (pat_off[i + 1] <= pat_off[i]) {
+            snprintf(msg, sizeof msg, "%s: pattern %u is empty", who, i);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        const u32 len = pat_off[i + 1] - pat_off[i];
+        if (len > KOLM_FIND_MAX_LEN) {
+            snprintf(msg, sizeof msg, "%s: pattern %u has %u positions (at most %u)", who, i, len, (u32)KOLM_FIND_MAX_LEN);
+            set_err(msg);
+            return KOLM_EARG;
+        }
+        *L = std::max(*L, len);
+    }
+    u32 ntab = 0, bad_pat = 0, bad_pos = 0;
+    if (!fcl::make_pats(bitmaps, pat_off, np, hp, &ntab, &bad_pat, &bad_pos)) {
+        snprintf(msg, sizeof msg,
+                 "%s: position %u of pattern %u is distinct table class %u of the call (at most %u classes that are no "
+                 "masked equality)",
+                 who, bad_pos, bad_pat, fcl::MAX_TABLES + 1, fcl::MAX_TABLES);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    return KOLM_OK;
+}
+
+const fcl::Pats* findcls_upload_pats(kolm_ctx* c, const fcl::Pats& hp) {
+    fcl::Pats* dp = c->get<fcl::Pats>("fc_pats", 1);
+    KOLM_HIP_CHECK(hipMemcpyAsync(dp, &hp, sizeof hp, hipMemcpyHostToDevice, c->stream));
+    return dp;
+}
+
+// find_group for class patterns: the same scratch, scan and emit loop around the class kernels
+void findcls_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fcl::Pats* dP, u32 np, u64 base, u64 limit,
+                   u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms,
+                   u64* more_than = nullptr) {
+    const u32 ntiles = fnd::tiles(n);
+    if (!ntiles) return;
+    hipStream_t s = c->stream;
+    u32* cnt = c->get<u32>("fd_cnt", (size_t)(np + 1) * ntiles);
+    u64* tot = c->get<u64>("fd_tot", fnd::MAX_PATTERNS + 1);
+    u64* tscan = c->get<u64>("fd_scan", (size_t)ntiles + 1);
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_findcls_count", n);
+        launch_findcls_count(buf, n, lo, shi, dP, np, cnt, s);
+    }
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)(np + 1) * ntiles);
+        launch_find_scan(cnt, ntiles, np, tot, tscan, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
+    u64 htot[fnd::MAX_PATTERNS + 1] = {};
+    KOLM_HIP_CHECK(hipMemcpyAsync(htot, tot, sizeof(u64) * (np + 1), hipMemcpyDeviceToHost, s));
+    c->sync();
+    ms += ev_ms(c->ev[6], c->ev[7]);
+    for (u32 i = 0; i < np; ++i) counts[i] += htot[i];
+    const u64 cap = std::min<u64>(fnd::stage_records(find_stage_bytes(), np), 0xFFFFFFFFull);
+    u32* dpos = nullptr;
+    u8* dwhich = nullptr;
+    std::vector<u32> hpos;
+    std::vector<u8> hwhich;
+    emit_matches(
+        c, ntiles, tscan, htot[np], offs.size(), limit, cap, more_than, launches, ms,
+        [&](u64 slots) {
+            dpos = c->get<u32>("fd_pos", slots);
+            dwhich = c->get<u8>("fd_which", slots);
+        },
+        [&](u32 t0, u32 t1, u64 recs, u32 slots) {
+            TScope t(c, KOLM_KT_EMIT, "k_findcls_emit", (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
+            launch_findcls_emit(buf, n, lo, shi, dP, np, t0, t1, tscan, dpos, dwhich, slots, s);
+        },
+        [&](u64 take) {
+            hpos.resize(take), hwhich.resize(take);
+            KOLM_HIP_CHECK(hipMemcpyAsync(hpos.data(), dpos, sizeof(u32) * take, hipMemcpyDeviceToHost, s));
+            KOLM_HIP_CHECK(hipMemcpyAsync(hwhich.data(), dwhich, take, hipMemcpyDeviceToHost, s));
+            c->sync();
+            for (u64 k = 0; k < take; ++k) offs.push_back(base + hpos[k]);
+            which.insert(which.end(), hwhich.begin(), hwhich.end());
+        });
+}
+
 }  // namespace
 
 extern "C" {
@@ -529,6 +624,96 @@ int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* 
     if (n && !offs) return KOLM_EARG;
     std::copy(r->f_offs.begin() + first, r->f_offs.begin() + first + n, offs);
     if (which) std::copy(r->f_which.begin() + first, r->f_which.begin() + first + n, which);
+    return KOLM_OK;
+}
+
+int kolm_find_classes_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t* bitmaps, const uint32_t* pat_off,
+                             uint32_t np, uint64_t max_results, uint64_t* counts, uint64_t* offs, uint8_t* which,
+                             uint64_t cap, uint64_t* nfound, double* ms) {
+    if (ms) *ms = 0.0;
+    if (nfound) *nfound = 0;
+    if (!c || !counts || !nfound) return KOLM_EARG;
+    u32 L = 0;
+    fcl::Pats hp;
+    if (int rc = findcls_check_pats("kolm_find_classes_device", bitmaps, pat_off, np, &L, hp)) return rc;
+    if (n >= (1ull << 31)) {
+        set_err("kolm_find_classes_device: the buffer must be smaller than 2^31 bytes");
+        return KOLM_EARG;
+    }
+    if ((n && !d_data) || (cap && (!offs || (!which && np > 1)))) return KOLM_EARG;
+    for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    if (n == 0) return KOLM_OK;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        c->active = c->stream;
+        const fcl::Pats* dP = findcls_upload_pats(c, hp);
+        std::vector<u64> o;
+        std::vector<u8> w;
+        u32 launches = 0;
+        double t = 0.0;
+        u64 more = cap;
+        findcls_group(c, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, dP, np, 0, max_results, counts, o, w, launches,
+                      t, &more);
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        if (ms) *ms = t;
+        if (more > cap) {
+            *nfound = more;
+            set_err("kolm_find_classes_device: result capacity too small");
+            return KOLM_ECAP;
+        }
+        *nfound = o.size();
+        std::copy(o.begin(), o.end(), offs);
+        if (which) std::copy(w.begin(), w.end(), which);
+        return KOLM_OK;
+    });
+}
+
+int kolm_reader_find_classes(kolm_reader* r, const uint8_t* bitmaps, const uint32_t* pat_off, uint32_t np, uint64_t lo,
+                             uint64_t hi, uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
+    if (stats) *stats = kolm_find_stats{};
+    if (nfound) *nfound = 0;
+    if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
+    // every argument check before the first launch: the patterns, the window, the selected blocks
+    u32 L = 0;
+    fcl::Pats hp;
+    if (int rc = findcls_check_pats("kolm_reader_find_classes", bitmaps, pat_off, np, &L, hp)) return rc;
+    RangePlan p;
+    kolm_find_stats st{};
+    st.patterns = np;
+    if (int rc = find_plan("kolm_reader_find_classes", r, lo, hi, p, st)) return rc;
+    for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    kolm_ctx* c = r->c;
+    std::vector<u64> offs;
+    std::vector<u8> which;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
+        if (p.sel.empty()) return KOLM_OK;
+        ReaderCall::enter(c);
+        const fcl::Pats* dP = findcls_upload_pats(c, hp);
+        if (int e = find_over_groups(r, p, lo, hi, L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
+                findcls_group(c, buf, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which,
+                              st.emit_launches, st.ms_find);
+            }))
+            return e;
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        return KOLM_OK;
+    });
+    if (rc) {  // no results leave a failed call
+        for (u32 i = 0; i < np; ++i) counts[i] = 0;
+        if (stats) *stats = st;
+        return rc;
+    }
+    for (u32 i = 0; i < np; ++i) st.matches += counts[i];
+    st.returned = offs.size();
+    *nfound = offs.size();
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->f_offs.swap(offs), r->f_which.swap(which);
+    }
+    if (stats) *stats = st;
     return KOLM_OK;
 }
 

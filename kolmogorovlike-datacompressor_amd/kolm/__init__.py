@@ -35,12 +35,14 @@ ids unchanged, containers still decodable by the reference).
 """
 from __future__ import annotations
 
+import re
 import struct
 import sys
 import zlib
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
-from . import _lib
+from . import _lib, classes
+from .classes import ClassPattern
 from ._lib import KolmError, KolmUnavailable, KolmVerifyError  # noqa: F401
 from .checksums import Checksums, KolmChecksumError, as_checksums
 from .lines import KolmLineIndexError, LineIndex, as_line_index, delim_byte
@@ -54,7 +56,7 @@ __all__ = [
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
-    "open_container", "Reader", "PatternSet", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
+    "open_container", "Reader", "PatternSet", "ClassPattern", "classes", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
     "Checksums", "KolmChecksumError", "crc32_blocks", "crc32_combine", "last_checksums", "checksums_of", "check",
     "LineIndex", "KolmLineIndexError", "line_index", "line_index_of", "last_line_index", "last_lines",
 ]
@@ -865,28 +867,91 @@ class Reader:
         _last_find = {}
         return offs, which, counts
 
-    def find(self, pattern, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None) -> List[int]:
+    def find(self, pattern, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None,
+             ignore_case: bool = False) -> List[int]:
         """Every offset o with start <= o, o + len(pattern) <= end and data[o:o + len] ==
         pattern, ascending, overlapping matches included; with `limit` the first `limit` of
         them.  Searched on the device where the decoded blocks lie (kolm_reader_find): only
         the offsets come back.  start / end are clipped to the data as slice bounds are
-        (negative values raise ValueError); the pattern is bytes-like, 1..256 bytes."""
+        (negative values raise ValueError); the pattern is bytes-like, 1..256 bytes.
+        ignore_case: ASCII letters match either case (the class path: find_classes of
+        ClassPattern.literal(pattern, True))."""
+        if ignore_case:
+            return self._search_classes(_folded([pattern]), start, end, limit)[0]
         return self._search([pattern], start, end, limit)[0]
 
     def find_many(self, patterns, start: int = 0, end: Optional[int] = None,
-                  limit: Optional[int] = None) -> List[Tuple[int, int]]:
+                  limit: Optional[int] = None, ignore_case: bool = False) -> List[Tuple[int, int]]:
         """(offset, pattern index) of every match of up to 16 patterns, sorted; identical
-        patterns are both reported."""
+        patterns are both reported.  ignore_case as find."""
+        if ignore_case:
+            offs, which, _ = self._search_classes(_folded(patterns), start, end, limit)
+            return list(zip(offs, which))
         offs, which, _ = self._search(patterns, start, end, limit)
         return list(zip(offs, which))
 
-    def count(self, pattern, start: int = 0, end: Optional[int] = None) -> int:
+    def count(self, pattern, start: int = 0, end: Optional[int] = None, ignore_case: bool = False) -> int:
         """len(find(pattern, start, end)) without listing the matches (no emit launch)."""
+        if ignore_case:
+            return self._search_classes(_folded([pattern]), start, end, 0)[2][0]
         return self._search([pattern], start, end, 0)[2][0]
 
-    def count_many(self, patterns, start: int = 0, end: Optional[int] = None) -> List[int]:
+    def count_many(self, patterns, start: int = 0, end: Optional[int] = None, ignore_case: bool = False) -> List[int]:
         """The number of matches of every pattern."""
+        if ignore_case:
+            return self._search_classes(_folded(patterns), start, end, 0)[2]
         return self._search(patterns, start, end, 0)[2]
+
+    def _search_classes(self, pats, start, end, limit):
+        """(offsets, pattern indices, counts) of the ClassPatterns `pats` in data[start:end]."""
+        global _last_find
+        h = self._handle()
+        if not 1 <= len(pats) <= _lib.KOLM_FIND_MAX_PATTERNS:
+            raise ValueError(f"{len(pats)} patterns (1..{_lib.KOLM_FIND_MAX_PATTERNS} are allowed)")
+        if classes.table_classes(pats) > classes.MAX_TABLE_CLASSES:
+            raise ValueError(f"the patterns hold {classes.table_classes(pats)} distinct classes that are no masked "
+                             f"equality (at most {classes.MAX_TABLE_CLASSES})")
+        start, end = int(start), self._total if end is None else int(end)
+        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
+            raise ValueError("start, end and limit must not be negative")
+        lo, hi = min(start, self._total), min(end, self._total)
+        if lo >= hi:  # nothing to search: no device call
+            return [], [], [0] * len(pats)
+        if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
+            data = self._read_host([(lo, hi - lo)])[0]
+            hits, counts = [], [0] * len(pats)
+            for i, p in enumerate(pats):  # the lookahead finds overlapping matches too
+                for m in re.finditer(b"(?=(" + p.regex() + b"))", data, re.DOTALL):
+                    hits.append((lo + m.start(), i))
+                    counts[i] += 1
+            hits.sort()
+            if limit is not None:
+                hits = hits[:int(limit)]
+            rd = dict(_last_read)
+            _last_find = {"host": True, "patterns": len(pats), "matches": sum(counts), "returned": len(hits),
+                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
+                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
+                          "ms_find": 0.0}
+            return [o for o, _ in hits], [i for _, i in hits], counts
+        offs, which, counts = _lib.reader_find_classes(h, [p.bitmaps for p in pats], lo, hi, limit)
+        _last_find = {}
+        return offs, which, counts
+
+    def find_classes(self, patterns, start: int = 0, end: Optional[int] = None,
+                     limit: Optional[int] = None) -> List[Tuple[int, int]]:
+        """(offset, pattern index) of every match of up to 16 class patterns in data[start:end],
+        sorted: o matches when data[o + j] lies in the pattern's class j for every j.
+        `patterns`: one ClassPattern or expression (bytes, compiled by kolm.classes.compile:
+        b"ERROR [0-9]{3}", rb"\\d{4}-\\d{2}-\\d{2}") or a sequence of them.  Overlapping matches,
+        identical patterns, start / end / limit as find_many; searched on the device
+        (kolm_reader_find_classes).  A call holds at most 64 distinct classes that are no masked
+        equality (kolm.classes)."""
+        offs, which, _ = self._search_classes(_class_patterns(patterns), start, end, limit)
+        return list(zip(offs, which))
+
+    def count_classes(self, patterns, start: int = 0, end: Optional[int] = None) -> List[int]:
+        """The number of matches of every class pattern (no emit launch)."""
+        return self._search_classes(_class_patterns(patterns), start, end, 0)[2]
 
     def _search_set(self, pset, start, end, limit):
         """(offsets, pattern indices, counts) of a PatternSet (or a sequence of patterns: a
@@ -1030,19 +1095,29 @@ class Reader:
         return self.read_many([(start, end - start)])[0].split(bytes([li.delim]))
 
     def grep(self, patterns, start: int = 0, end: Optional[int] = None,
-             limit: Optional[int] = None) -> List[Tuple[int, bytes]]:
+             limit: Optional[int] = None, ignore_case: bool = False) -> List[Tuple[int, bytes]]:
         """(line number, line) of the distinct lines that own at least one match of the patterns in
         data[start:end], ascending; with `limit` the first `limit` lines.  A match belongs to the
         line its first byte lies in (also when the pattern contains the delimiter).  `patterns`: one
         bytes-like pattern, a sequence of them (more than 16: a temporary PatternSet) or a
         PatternSet.  Built from what exists: find_many / find_set, line_of on the match offsets,
-        line_spans, read_many."""
+        line_spans, read_many.  Up to 16 patterns may also be ClassPatterns (kolm.classes), or
+        literals with ignore_case (ASCII letters match either case): the class path of
+        find_classes; a PatternSet or more than 16 patterns with either raise ValueError."""
         self._lines()
         if limit is not None and int(limit) < 0:
             raise ValueError("start, end and limit must not be negative")
-        if isinstance(patterns, (bytes, bytearray, memoryview)):
+        if isinstance(patterns, (bytes, bytearray, memoryview, ClassPattern)):
             patterns = [patterns]
-        if isinstance(patterns, PatternSet) or len(patterns) > _lib.KOLM_FIND_MAX_PATTERNS:
+        if ignore_case or (not isinstance(patterns, PatternSet) and any(isinstance(p, ClassPattern) for p in patterns)):
+            if isinstance(patterns, PatternSet) or len(patterns) > _lib.KOLM_FIND_MAX_PATTERNS:
+                raise ValueError("ignore_case and class patterns take at most "
+                                 f"{_lib.KOLM_FIND_MAX_PATTERNS} patterns and no PatternSet")
+            pats = [classes.as_pattern(p, ignore_case) if isinstance(p, ClassPattern)
+                    else ClassPattern.literal(p, ignore_case) for p in patterns]
+            offs, which, _ = self._search_classes(pats, start, end, None)
+            hits = list(zip(offs, which))
+        elif isinstance(patterns, PatternSet) or len(patterns) > _lib.KOLM_FIND_MAX_PATTERNS:
             hits = self.find_set(patterns, start, end)
         else:
             hits = self.find_many(patterns, start, end)
@@ -1128,7 +1203,7 @@ _last_lines: Dict[str, Any] = {}
 
 def last_find() -> Dict[str, Any]:
     """kolm_find_stats of the last Reader.find / find_many / count / count_many / find_set /
-    count_set: patterns,
+    count_set / find_classes / count_classes: patterns,
     matches (total, whatever the limit), returned, blocks_decoded, groups, emit_launches,
     bytes_decoded, bytes_scanned, ms_decode, ms_find (a call served on the host reports its
     blocks and matches with groups = 0 and "host": True)."""
@@ -1138,10 +1213,24 @@ def last_find() -> Dict[str, Any]:
 _last_find: Dict[str, Any] = {}
 
 
+def _folded(patterns) -> List[ClassPattern]:
+    """The literals of an ignore_case search as class patterns."""
+    return [ClassPattern.literal(p, True) for p in _lib.find_patterns(patterns)]
+
+
+def _class_patterns(patterns) -> List[ClassPattern]:
+    """One ClassPattern or expression, or a sequence of them, as a list of ClassPatterns."""
+    if isinstance(patterns, (bytes, bytearray, memoryview, ClassPattern)):
+        patterns = [patterns]
+    return [classes.as_pattern(p) for p in patterns]
+
+
 def find(container: bytes, pattern, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None,
-         checksums=None) -> List[int]:
+         checksums=None, ignore_case: bool = False) -> List[int]:
     """Reader.find over `container`: opens, searches, closes."""
     with Reader(container, checksums=checksums) as r:
+        if ignore_case:
+            return r.find(pattern, start, end, limit, ignore_case=True)
         return r.find(pattern, start, end, limit)
 
 

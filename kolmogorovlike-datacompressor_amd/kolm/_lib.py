@@ -314,6 +314,9 @@ SIGNATURES = [
                                ctypes.POINTER(ctypes.c_double)]),
     ("kolm_reader_find", I32, [P, P, P, U32, U64, U64, U64, P, ctypes.POINTER(U64), ctypes.POINTER(FindStats)]),
     ("kolm_reader_find_copy", I32, [P, U64, U64, P, P]),
+    ("kolm_find_classes_device", I32, [P, P, U64, P, P, U32, U64, P, P, P, U64, ctypes.POINTER(U64),
+                                       ctypes.POINTER(ctypes.c_double)]),
+    ("kolm_reader_find_classes", I32, [P, P, P, U32, U64, U64, U64, P, ctypes.POINTER(U64), ctypes.POINTER(FindStats)]),
     ("kolm_patset_create", I32, [P, P, P, U32, ctypes.POINTER(P)]),
     ("kolm_patset_free", None, [P]),
     ("kolm_patset_info", I32, [P, ctypes.POINTER(PatsetInfo)]),
@@ -1393,6 +1396,65 @@ def reader_find(h, patterns, lo: int, hi: int, limit=None):
     lim = NO_LIMIT if limit is None else int(limit)
     _read_check(load().kolm_reader_find(h, flat.ctypes.data, off.ctypes.data, len(pats), lo, hi, lim, counts.ctypes.data,
                                         ctypes.byref(nfound), ctypes.byref(st)))
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint8)
+    check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
+    _last_find = st.as_dict()
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]]
+
+
+# ---- class patterns (kolm_find_classes_device, kolm_reader_find_classes) --------------------
+# A pattern is passed as its positions' 32-byte bitmaps back to back (ClassPattern.bitmaps).
+
+def _class_arrays(pats):
+    off = np.zeros(len(pats) + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(p) // 32 for p in pats])
+    flat = np.frombuffer(b"".join(bytes(p) for p in pats) + bytes(32), dtype=np.uint8)
+    return flat, off
+
+
+def find_classes_device(ctx, dptr: int, n: int, bitmaps, limit=None):
+    """kolm_find_classes_device over the n bytes at the device address dptr; returns what
+    find_device returns.  The patterns are passed as given."""
+    pats = list(bitmaps)
+    flat, off = _class_arrays(pats)
+    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
+    nfound, ms = U64(0), ctypes.c_double(0.0)
+    lim = NO_LIMIT if limit is None else int(limit)
+    L = load()
+    rc = L.kolm_find_classes_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim, counts.ctypes.data,
+                                    None, None, 0, ctypes.byref(nfound), ctypes.byref(ms))
+    if rc == -1:
+        raise ValueError(L.kolm_last_error().decode())
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint8)
+    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
+        rc = L.kolm_find_classes_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim,
+                                        counts.ctypes.data, offs.ctypes.data, which.ctypes.data, k, ctypes.byref(nfound),
+                                        ctypes.byref(ms))
+    check(rc)
+    k = int(nfound.value)
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]], ms.value
+
+
+def find_classes_bytes(data, bitmaps, limit=None, device: int = None, data_offset: int = 0):
+    """Uploads data data_offset (0..15) bytes into a buffer and searches it (find_classes_device)."""
+    return _on_device(data, data_offset, device, lambda ctx, p: find_classes_device(ctx, p, len(data), bitmaps, limit))
+
+
+def reader_find_classes(h, bitmaps, lo: int, hi: int, limit=None):
+    """kolm_reader_find_classes + kolm_reader_find_copy; returns and raises as reader_find."""
+    global _last_find
+    pats = list(bitmaps)
+    flat, off = _class_arrays(pats)
+    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
+    nfound = U64(0)
+    st = FindStats()
+    lim = NO_LIMIT if limit is None else int(limit)
+    _read_check(load().kolm_reader_find_classes(h, flat.ctypes.data, off.ctypes.data, len(pats), lo, hi, lim,
+                                                counts.ctypes.data, ctypes.byref(nfound), ctypes.byref(st)))
     k = int(nfound.value)
     offs = np.zeros(max(k, 1), dtype=np.uint64)
     which = np.zeros(max(k, 1), dtype=np.uint8)
