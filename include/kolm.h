@@ -510,6 +510,42 @@ int kolm_find_classes_device(kolm_ctx* ctx, const void* d_data, uint64_t n, cons
 int kolm_reader_find_classes(kolm_reader* r, const uint8_t* bitmaps, const uint32_t* pat_off, uint32_t np, uint64_t lo,
                              uint64_t hi, uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats);
 
+/* ---- regular expressions: one automaton for up to 16 expressions ------------------------------- */
+/* The np expressions (1..KOLM_FIND_MAX_PATTERNS) of a call are passed compiled, as one deterministic
+ * automaton (kolm/regex.py builds it; csrc/findrx_core.h walks it):
+ *   cls_map  256 bytes: the class of every byte value, each < ncls (1..256)
+ *   table    nstates x ncls transitions, row-major: table[s * ncls + c] is the state after state s
+ *            reads a byte of class c.  State 0 is dead and state 1 accepts; both are absorbing and
+ *            their rows are all zero.  nstates * ncls <= KOLM_RX_MAX_ENTRIES (32 KiB of LDS).
+ *   starts   the start state of every expression, each in [2, nstates): no expression matches the
+ *            empty string
+ * (o, i) is a match iff lo <= o and there is a k in 1..KOLM_FIND_MAX_LEN with o + k <= hi such that
+ * the walk from starts[i] over data[o .. o + k) ends in state 1: expression i matches data[o:o + k]
+ * exactly.  For the syntax of kolm.regex.compile that is
+ *   re.compile(b"(?:" + expr + b")", re.DOTALL [| re.IGNORECASE]).match(data, o, min(hi, o + 256)) is not None.
+ * Every such start is reported, overlapping ones and those of identical expressions included, sorted
+ * by (offset, expression).  Only starts are reported: a match has no length here (greedy, lazy
+ * and leftmost-longest differ, and none of them is decided per start).  The witness cap of
+ * KOLM_FIND_MAX_LEN = 256 bytes is the hold-back the group loop supports: a start whose shortest
+ * match is longer is not a match.  The walk takes at most 256 steps whatever the table holds.
+ * Counting, max_results, the exact totals under a limit and the independence of KOLM_READ_BYTES /
+ * KOLM_FIND_STAGE are those of the search above, as are the tile geometry, the scan, the staged
+ * emit, the hold-back between groups (its length derived from the table by the library) and the
+ * checksum rule.
+ * KOLM_EARG before any launch, the message naming what is wrong: np = 0 or np > 16, ncls = 0 or
+ * > 256, fewer than 3 states, more than KOLM_RX_MAX_ENTRIES entries, a class id >= ncls, an entry
+ * >= nstates, a non-zero entry in row 0 or 1, a start outside [2, nstates). */
+#define KOLM_RX_MAX_ENTRIES 16384
+/* kolm_find_device for an automaton (KOLM_ECAP included). */
+int kolm_find_dfa_device(kolm_ctx* ctx, const void* d_data, uint64_t n, const uint8_t* cls_map, const uint16_t* table,
+                         uint32_t nstates, uint32_t ncls, const uint16_t* starts, uint32_t np, uint64_t max_results,
+                         uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap, uint64_t* nfound, double* ms);
+/* kolm_reader_find for an automaton: the result stays in the reader until its next find of any
+ * kind and is copied out by kolm_reader_find_copy. */
+int kolm_reader_find_dfa(kolm_reader* r, const uint8_t* cls_map, const uint16_t* table, uint32_t nstates, uint32_t ncls,
+                         const uint16_t* starts, uint32_t np, uint64_t lo, uint64_t hi, uint64_t max_results,
+                         uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats);
+
 /* ---- pattern sets: up to 65 536 patterns in one pass ----------------------------------------- */
 /* A set holds np patterns (1..KOLM_FIND_SET_MAX_PATTERNS) of 1..KOLM_FIND_MAX_LEN bytes each,
  * pairwise distinct: two equal patterns are refused with KOLM_EARG, the message naming both

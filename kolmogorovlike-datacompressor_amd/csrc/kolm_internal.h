@@ -738,6 +738,18 @@ void launch_findcls_emit(const u8* buf, u32 n, u32 lo, u32 shi, const fcl::Pats*
                          const u64* tscan, u32* out_pos, u8* out_which, u32 cap, hipStream_t s);
 }  // namespace kolm
 
+// ---- k_findrx.hip: search of a resident buffer for regular expressions (findrx_core.h) ----
+#include "findrx_core.h"
+namespace kolm {
+// as launch_find_count / launch_find_emit (launch_find_scan between them).  img: the device image
+// of the call's automaton, the class map (frx::MAP bytes) and behind it the table in
+// frx::padded_entries(nstates, ncls) entries; st: the expressions' start states
+void launch_findrx_count(const u8* buf, u32 n, u32 lo, u32 shi, const u8* img, u32 nstates, u32 ncls,
+                         const frx::Starts& st, u32 np, u32* cnt, hipStream_t s);
+void launch_findrx_emit(const u8* buf, u32 n, u32 lo, u32 shi, const u8* img, u32 nstates, u32 ncls, const frx::Starts& st,
+                        u32 np, u32 t0, u32 t1, const u64* tscan, u32* out_pos, u8* out_which, u32 cap, hipStream_t s);
+}  // namespace kolm
+
 #define KOLM_HIP_CHECK(x)                                              \
     do {                                                               \
         hipError_t e_ = (x);                                           \

@@ -520,6 +520,90 @@ void findcls_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fcl
         });
 }
 
+// ---- regular expressions (findrx_core.h, k_findrx.hip) ----
+
+// The automaton of a call, checked (frx::validate) and laid out as the kernels read it.
+struct RxCall {
+    std::vector<u8> img;  // the class map, then the table in whole 16-byte words
+    frx::Starts st{};
+    u32 nstates = 0, ncls = 0, np = 0;
+    u32 L = 0;  // the hold-back, from the table itself
+};
+
+int findrx_check(const char* who, const uint8_t* cls_map, const uint16_t* table, u32 nstates, u32 ncls, const uint16_t* starts,
+                 u32 np, RxCall& rx) {
+    char why[200], msg[280];
+    if (frx::validate(cls_map, table, nstates, ncls, starts, np, why, sizeof why)) {
+        snprintf(msg, sizeof msg, "%s: %s", who, why);
+        set_err(msg);
+        return KOLM_EARG;
+    }
+    rx.nstates = nstates, rx.ncls = ncls, rx.np = np;
+    rx.img.assign(frx::MAP + sizeof(uint16_t) * (size_t)frx::padded_entries(nstates, ncls), 0);
+    memcpy(rx.img.data(), cls_map, frx::MAP);
+    memcpy(rx.img.data() + frx::MAP, table, sizeof(uint16_t) * (size_t)nstates * ncls);
+    for (u32 i = 0; i < np; ++i) rx.st.s[i] = starts[i];
+    std::vector<u8> scratch(2 * (size_t)nstates);
+    rx.L = frx::hold_back(table, nstates, ncls, starts, np, scratch.data());
+    return KOLM_OK;
+}
+
+const u8* findrx_upload(kolm_ctx* c, const RxCall& rx) {
+    u8* d = c->get<u8>("rx_img", rx.img.size());
+    KOLM_HIP_CHECK(hipMemcpyAsync(d, rx.img.data(), rx.img.size(), hipMemcpyHostToDevice, c->stream));
+    return d;
+}
+
+// find_group for regular expressions: the same scratch, scan and emit loop around the DFA kernels
+void findrx_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const u8* img, const RxCall& rx, u64 base, u64 limit,
+                  u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms,
+                  u64* more_than = nullptr) {
+    const u32 ntiles = fnd::tiles(n), np = rx.np;
+    if (!ntiles) return;
+    hipStream_t s = c->stream;
+    u32* cnt = c->get<u32>("fd_cnt", (size_t)(np + 1) * ntiles);
+    u64* tot = c->get<u64>("fd_tot", fnd::MAX_PATTERNS + 1);
+    u64* tscan = c->get<u64>("fd_scan", (size_t)ntiles + 1);
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_findrx_count", n);
+        launch_findrx_count(buf, n, lo, shi, img, rx.nstates, rx.ncls, rx.st, np, cnt, s);
+    }
+    {
+        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)(np + 1) * ntiles);
+        launch_find_scan(cnt, ntiles, np, tot, tscan, s);
+    }
+    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
+    u64 htot[fnd::MAX_PATTERNS + 1] = {};
+    KOLM_HIP_CHECK(hipMemcpyAsync(htot, tot, sizeof(u64) * (np + 1), hipMemcpyDeviceToHost, s));
+    c->sync();
+    ms += ev_ms(c->ev[6], c->ev[7]);
+    for (u32 i = 0; i < np; ++i) counts[i] += htot[i];
+    const u64 cap = std::min<u64>(fnd::stage_records(find_stage_bytes(), np), 0xFFFFFFFFull);
+    u32* dpos = nullptr;
+    u8* dwhich = nullptr;
+    std::vector<u32> hpos;
+    std::vector<u8> hwhich;
+    emit_matches(
+        c, ntiles, tscan, htot[np], offs.size(), limit, cap, more_than, launches, ms,
+        [&](u64 slots) {
+            dpos = c->get<u32>("fd_pos", slots);
+            dwhich = c->get<u8>("fd_which", slots);
+        },
+        [&](u32 t0, u32 t1, u64 recs, u32 slots) {
+            TScope t(c, KOLM_KT_EMIT, "k_findrx_emit", (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
+            launch_findrx_emit(buf, n, lo, shi, img, rx.nstates, rx.ncls, rx.st, np, t0, t1, tscan, dpos, dwhich, slots, s);
+        },
+        [&](u64 take) {
+            hpos.resize(take), hwhich.resize(take);
+            KOLM_HIP_CHECK(hipMemcpyAsync(hpos.data(), dpos, sizeof(u32) * take, hipMemcpyDeviceToHost, s));
+            KOLM_HIP_CHECK(hipMemcpyAsync(hwhich.data(), dwhich, take, hipMemcpyDeviceToHost, s));
+            c->sync();
+            for (u64 k = 0; k < take; ++k) offs.push_back(base + hpos[k]);
+            which.insert(which.end(), hwhich.begin(), hwhich.end());
+        });
+}
+
 }  // namespace
 
 extern "C" {
@@ -696,6 +780,95 @@ int kolm_reader_find_classes(kolm_reader* r, const uint8_t* bitmaps, const uint3
         if (int e = find_over_groups(r, p, lo, hi, L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
                 findcls_group(c, buf, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which,
                               st.emit_launches, st.ms_find);
+            }))
+            return e;
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        return KOLM_OK;
+    });
+    if (rc) {  // no results leave a failed call
+        for (u32 i = 0; i < np; ++i) counts[i] = 0;
+        if (stats) *stats = st;
+        return rc;
+    }
+    for (u32 i = 0; i < np; ++i) st.matches += counts[i];
+    st.returned = offs.size();
+    *nfound = offs.size();
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->f_offs.swap(offs), r->f_which.swap(which);
+    }
+    if (stats) *stats = st;
+    return KOLM_OK;
+}
+
+int kolm_find_dfa_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t* cls_map, const uint16_t* table,
+                         uint32_t nstates, uint32_t ncls, const uint16_t* starts, uint32_t np, uint64_t max_results,
+                         uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap, uint64_t* nfound, double* ms) {
+    if (ms) *ms = 0.0;
+    if (nfound) *nfound = 0;
+    if (!c || !counts || !nfound) return KOLM_EARG;
+    RxCall rx;
+    if (int rc = findrx_check("kolm_find_dfa_device", cls_map, table, nstates, ncls, starts, np, rx)) return rc;
+    if (n >= (1ull << 31)) {
+        set_err("kolm_find_dfa_device: the buffer must be smaller than 2^31 bytes");
+        return KOLM_EARG;
+    }
+    if ((n && !d_data) || (cap && (!offs || (!which && np > 1)))) return KOLM_EARG;
+    for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    if (n == 0) return KOLM_OK;
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        KOLM_HIP_CHECK(hipSetDevice(c->device));
+        c->timing_reset();
+        c->active = c->stream;
+        const u8* img = findrx_upload(c, rx);
+        std::vector<u64> o;
+        std::vector<u8> w;
+        u32 launches = 0;
+        double t = 0.0;
+        u64 more = cap;
+        findrx_group(c, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, img, rx, 0, max_results, counts, o, w, launches, t,
+                     &more);
+        if (c->timing) c->timing_collect_tail(0, nullptr);
+        if (ms) *ms = t;
+        if (more > cap) {
+            *nfound = more;
+            set_err("kolm_find_dfa_device: result capacity too small");
+            return KOLM_ECAP;
+        }
+        *nfound = o.size();
+        std::copy(o.begin(), o.end(), offs);
+        if (which) std::copy(w.begin(), w.end(), which);
+        return KOLM_OK;
+    });
+}
+
+int kolm_reader_find_dfa(kolm_reader* r, const uint8_t* cls_map, const uint16_t* table, uint32_t nstates, uint32_t ncls,
+                         const uint16_t* starts, uint32_t np, uint64_t lo, uint64_t hi, uint64_t max_results,
+                         uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
+    if (stats) *stats = kolm_find_stats{};
+    if (nfound) *nfound = 0;
+    if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
+    // every argument check before the first launch: the automaton, the window, the selected blocks
+    RxCall rx;
+    if (int rc = findrx_check("kolm_reader_find_dfa", cls_map, table, nstates, ncls, starts, np, rx)) return rc;
+    RangePlan p;
+    kolm_find_stats st{};
+    st.patterns = np;
+    if (int rc = find_plan("kolm_reader_find_dfa", r, lo, hi, p, st)) return rc;
+    for (u32 i = 0; i < np; ++i) counts[i] = 0;
+    kolm_ctx* c = r->c;
+    std::vector<u64> offs;
+    std::vector<u8> which;
+    int rc = guarded([&] {
+        std::lock_guard<std::mutex> g(c->mu);
+        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
+        if (p.sel.empty()) return KOLM_OK;
+        ReaderCall::enter(c);
+        const u8* img = findrx_upload(c, rx);
+        if (int e = find_over_groups(r, p, lo, hi, rx.L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
+                findrx_group(c, buf, gs.n, gs.lo, gs.shi, img, rx, gs.start, max_results, counts, offs, which,
+                             st.emit_launches, st.ms_find);
             }))
             return e;
         if (c->timing) c->timing_collect_tail(0, nullptr);

@@ -41,8 +41,9 @@ import sys
 import zlib
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
-from . import _lib, classes
+from . import _lib, classes, regex
 from .classes import ClassPattern
+from .regex import Regex
 from ._lib import KolmError, KolmUnavailable, KolmVerifyError  # noqa: F401
 from .checksums import Checksums, KolmChecksumError, as_checksums
 from .lines import KolmLineIndexError, LineIndex, as_line_index, delim_byte
@@ -56,7 +57,7 @@ __all__ = [
     "rice_encode", "encode_lz77", "encode_bbwt_mtf_rice", "encode_raw", "encode_xor",
     "encode_lfsr_predict", "repair_compress", "encode_new_pipeline", "decode_new_pipeline", "uleb128_encode", "uleb128_decode_stream", "CANDIDATE_NAMES",
     "KolmUnavailable", "KolmError", "last_stats", "KolmVerifyError", "last_verify", "verify",
-    "open_container", "Reader", "PatternSet", "ClassPattern", "classes", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
+    "open_container", "Reader", "PatternSet", "ClassPattern", "classes", "Regex", "regex", "find_regex", "last_read", "find", "last_find", "last_dedup", "duplicate_blocks", "block_fingerprints",
     "Checksums", "KolmChecksumError", "crc32_blocks", "crc32_combine", "last_checksums", "checksums_of", "check",
     "LineIndex", "KolmLineIndexError", "line_index", "line_index_of", "last_line_index", "last_lines",
 ]
@@ -953,6 +954,56 @@ class Reader:
         """The number of matches of every class pattern (no emit launch)."""
         return self._search_classes(_class_patterns(patterns), start, end, 0)[2]
 
+    def _search_regex(self, rxs, start, end, limit):
+        """(offsets, expression indices, counts) of the Regex objects `rxs` in data[start:end]."""
+        global _last_find
+        h = self._handle()
+        table = regex.table(rxs)  # ValueError: no expression, more than 16, too large an automaton
+        start, end = int(start), self._total if end is None else int(end)
+        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
+            raise ValueError("start, end and limit must not be negative")
+        lo, hi = min(start, self._total), min(end, self._total)
+        if lo >= hi:  # nothing to search: no device call
+            return [], [], [0] * len(rxs)
+        if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
+            data = self._read_host([(lo, hi - lo)])[0]
+            hits, counts = [], [0] * len(rxs)
+            for i, r in enumerate(rxs):  # the rule of kolm.h, offset by offset
+                for o in range(len(data)):
+                    if r.host.match(data, o, min(len(data), o + regex.MAX_WALK)) is not None:
+                        hits.append((lo + o, i))
+                        counts[i] += 1
+            hits.sort()
+            if limit is not None:
+                hits = hits[:int(limit)]
+            rd = dict(_last_read)
+            _last_find = {"host": True, "patterns": len(rxs), "matches": sum(counts), "returned": len(hits),
+                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
+                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
+                          "ms_find": 0.0}
+            return [o for o, _ in hits], [i for _, i in hits], counts
+        offs, which, counts = _lib.reader_find_dfa(h, table, lo, hi, limit)
+        _last_find = {}
+        return offs, which, counts
+
+    def find_regex(self, exprs, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None,
+                   ignore_case: bool = False) -> List[Tuple[int, int]]:
+        """(offset, expression index) of every start of a match of up to 16 regular expressions in
+        data[start:end], sorted: o is a match of expression i when some data[o:o + k], 1 <= k <= 256
+        and o + k <= end, is matched by it exactly, which is
+        re.compile(b"(?:" + expr + b")", re.DOTALL).match(data, o, min(end, o + 256)) is not None.
+        `exprs`: one expression (bytes, compiled by kolm.regex.compile: rb"ERROR|WARN(ING)?",
+        rb"https?://[^ ]+"), Regex or ClassPattern, or a sequence of them.  Overlapping matches,
+        identical expressions, start / end / limit as find_many; only starts are reported, no
+        lengths.  Searched on the device (kolm_reader_find_dfa): the expressions become one
+        automaton of at most 16 384 transitions (kolm.regex)."""
+        offs, which, _ = self._search_regex(regex.as_list(exprs, ignore_case), start, end, limit)
+        return list(zip(offs, which))
+
+    def count_regex(self, exprs, start: int = 0, end: Optional[int] = None, ignore_case: bool = False) -> List[int]:
+        """The number of matching starts of every expression (no emit launch)."""
+        return self._search_regex(regex.as_list(exprs, ignore_case), start, end, 0)[2]
+
     def _search_set(self, pset, start, end, limit):
         """(offsets, pattern indices, counts) of a PatternSet (or a sequence of patterns: a
         temporary set, closed before returning) in data[start:end]."""
@@ -1103,13 +1154,24 @@ class Reader:
         PatternSet.  Built from what exists: find_many / find_set, line_of on the match offsets,
         line_spans, read_many.  Up to 16 patterns may also be ClassPatterns (kolm.classes), or
         literals with ignore_case (ASCII letters match either case): the class path of
-        find_classes; a PatternSet or more than 16 patterns with either raise ValueError."""
+        find_classes; a PatternSet or more than 16 patterns with either raise ValueError.  Regex
+        objects (kolm.regex.compile) among up to 16 patterns put the call on the path of
+        find_regex, literals and ClassPatterns next to them converted; a PatternSet or more
+        than 16 patterns with them raise ValueError too."""
         self._lines()
         if limit is not None and int(limit) < 0:
             raise ValueError("start, end and limit must not be negative")
-        if isinstance(patterns, (bytes, bytearray, memoryview, ClassPattern)):
+        if isinstance(patterns, (bytes, bytearray, memoryview, ClassPattern, Regex)):
             patterns = [patterns]
-        if ignore_case or (not isinstance(patterns, PatternSet) and any(isinstance(p, ClassPattern) for p in patterns)):
+        if not isinstance(patterns, PatternSet) and any(isinstance(p, Regex) for p in patterns):
+            if len(patterns) > _lib.KOLM_FIND_MAX_PATTERNS or any(isinstance(p, PatternSet) for p in patterns):
+                raise ValueError(f"regular expressions take at most {_lib.KOLM_FIND_MAX_PATTERNS} patterns and no "
+                                 "PatternSet")
+            rxs = [regex.as_regex(p, ignore_case) if isinstance(p, (Regex, ClassPattern))
+                   else Regex.literal(p, ignore_case) for p in patterns]
+            offs, which, _ = self._search_regex(rxs, start, end, None)
+            hits = list(zip(offs, which))
+        elif ignore_case or (not isinstance(patterns, PatternSet) and any(isinstance(p, ClassPattern) for p in patterns)):
             if isinstance(patterns, PatternSet) or len(patterns) > _lib.KOLM_FIND_MAX_PATTERNS:
                 raise ValueError("ignore_case and class patterns take at most "
                                  f"{_lib.KOLM_FIND_MAX_PATTERNS} patterns and no PatternSet")
@@ -1203,7 +1265,7 @@ _last_lines: Dict[str, Any] = {}
 
 def last_find() -> Dict[str, Any]:
     """kolm_find_stats of the last Reader.find / find_many / count / count_many / find_set /
-    count_set / find_classes / count_classes: patterns,
+    count_set / find_classes / count_classes / find_regex / count_regex: patterns,
     matches (total, whatever the limit), returned, blocks_decoded, groups, emit_launches,
     bytes_decoded, bytes_scanned, ms_decode, ms_find (a call served on the host reports its
     blocks and matches with groups = 0 and "host": True)."""
@@ -1223,6 +1285,13 @@ def _class_patterns(patterns) -> List[ClassPattern]:
     if isinstance(patterns, (bytes, bytearray, memoryview, ClassPattern)):
         patterns = [patterns]
     return [classes.as_pattern(p) for p in patterns]
+
+
+def find_regex(container: bytes, expr, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None,
+               checksums=None, ignore_case: bool = False) -> List[int]:
+    """Reader.find_regex of one expression over `container`: opens, searches, closes; the offsets."""
+    with Reader(container, checksums=checksums) as r:
+        return [o for o, _ in r.find_regex([expr], start, end, limit, ignore_case)]
 
 
 def find(container: bytes, pattern, start: int = 0, end: Optional[int] = None, limit: Optional[int] = None,

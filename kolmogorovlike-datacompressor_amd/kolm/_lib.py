@@ -317,6 +317,10 @@ SIGNATURES = [
     ("kolm_find_classes_device", I32, [P, P, U64, P, P, U32, U64, P, P, P, U64, ctypes.POINTER(U64),
                                        ctypes.POINTER(ctypes.c_double)]),
     ("kolm_reader_find_classes", I32, [P, P, P, U32, U64, U64, U64, P, ctypes.POINTER(U64), ctypes.POINTER(FindStats)]),
+    ("kolm_find_dfa_device", I32, [P, P, U64, P, P, U32, U32, P, U32, U64, P, P, P, U64, ctypes.POINTER(U64),
+                                   ctypes.POINTER(ctypes.c_double)]),
+    ("kolm_reader_find_dfa", I32, [P, P, P, U32, U32, P, U32, U64, U64, U64, P, ctypes.POINTER(U64),
+                                   ctypes.POINTER(FindStats)]),
     ("kolm_patset_create", I32, [P, P, P, U32, ctypes.POINTER(P)]),
     ("kolm_patset_free", None, [P]),
     ("kolm_patset_info", I32, [P, ctypes.POINTER(PatsetInfo)]),
@@ -339,6 +343,7 @@ SIGNATURES = [
 KOLM_FIND_MAX_PATTERNS = 16
 KOLM_FIND_MAX_LEN = 256
 KOLM_FIND_SET_MAX_PATTERNS = 65536
+KOLM_RX_MAX_ENTRIES = 16384
 KOLM_COMM_ID_BYTES = 128
 KOLM_ECAP = -2
 KOLM_ERCCL = -4
@@ -1461,6 +1466,65 @@ def reader_find_classes(h, bitmaps, lo: int, hi: int, limit=None):
     check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
     _last_find = st.as_dict()
     return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]]
+
+
+# ---- regular expressions (kolm_find_dfa_device, kolm_reader_find_dfa) -----------------------
+# The expressions of a call are passed as one automaton: a kolm.regex.Table, or anything with its
+# cls_map (256 bytes), T (a (nstates, ncls) uint16 array) and starts.
+
+def _dfa_arrays(table):
+    cls = np.frombuffer(bytes(table.cls_map), dtype=np.uint8)
+    T = np.ascontiguousarray(table.T, dtype=np.uint16)
+    starts = np.asarray(list(table.starts) + [0], dtype=np.uint16)
+    if cls.size != 256 or T.ndim != 2:
+        raise ValueError("an automaton has a class map of 256 bytes and a table of states x classes")
+    return cls, T, starts, len(table.starts)
+
+
+def find_dfa_device(ctx, dptr: int, n: int, table, limit=None):
+    """kolm_find_dfa_device over the n bytes at the device address dptr; returns what find_device
+    returns.  The automaton is passed as given."""
+    cls, T, starts, ne = _dfa_arrays(table)
+    counts = np.zeros(max(ne, 1), dtype=np.uint64)
+    nfound, ms = U64(0), ctypes.c_double(0.0)
+    lim = NO_LIMIT if limit is None else int(limit)
+    L = load()
+    args = (cls.ctypes.data, T.ctypes.data, T.shape[0], T.shape[1], starts.ctypes.data, ne, lim, counts.ctypes.data)
+    rc = L.kolm_find_dfa_device(ctx, dptr, n, *args, None, None, 0, ctypes.byref(nfound), ctypes.byref(ms))
+    if rc == -1:
+        raise ValueError(L.kolm_last_error().decode())
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint8)
+    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
+        rc = L.kolm_find_dfa_device(ctx, dptr, n, *args, offs.ctypes.data, which.ctypes.data, k, ctypes.byref(nfound),
+                                    ctypes.byref(ms))
+    check(rc)
+    k = int(nfound.value)
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:ne]], ms.value
+
+
+def find_dfa_bytes(data, table, limit=None, device: int = None, data_offset: int = 0):
+    """Uploads data data_offset (0..15) bytes into a buffer and searches it (find_dfa_device)."""
+    return _on_device(data, data_offset, device, lambda ctx, p: find_dfa_device(ctx, p, len(data), table, limit))
+
+
+def reader_find_dfa(h, table, lo: int, hi: int, limit=None):
+    """kolm_reader_find_dfa + kolm_reader_find_copy; returns and raises as reader_find."""
+    global _last_find
+    cls, T, starts, ne = _dfa_arrays(table)
+    counts = np.zeros(max(ne, 1), dtype=np.uint64)
+    nfound = U64(0)
+    st = FindStats()
+    lim = NO_LIMIT if limit is None else int(limit)
+    _read_check(load().kolm_reader_find_dfa(h, cls.ctypes.data, T.ctypes.data, T.shape[0], T.shape[1], starts.ctypes.data, ne,
+                                            lo, hi, lim, counts.ctypes.data, ctypes.byref(nfound), ctypes.byref(st)))
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=np.uint8)
+    check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
+    _last_find = st.as_dict()
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:ne]]
 
 
 # ---- pattern sets (kolm_patset_create, kolm_find_set_device, kolm_reader_find_set) ---------
