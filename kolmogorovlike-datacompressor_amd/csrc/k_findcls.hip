@@ -1,7 +1,7 @@
 // Search of a resident buffer for class patterns on gfx950 (findcls_core.h): every match of up to
 // 16 patterns of 1..256 byte classes, counted and listed in (position, pattern) order.  The tile
-// geometry, the count columns, k_find_scan between the two kernels and the record slots are
-// k_find.hip's; ordering is by launch boundaries only: no spinning, no tickets, no atomics.
+// geometry, the count columns and the record slots are the tile skeleton's (find_tile.h), k_find_scan
+// runs between the two kernels; ordering is by launch boundaries only: no spinning, no tickets, no atomics.
 //   k_findcls_count  one workgroup per 4 KiB tile, 256 threads x 16 positions.  The call's table
 //                    T (2 KiB) and, of every pattern, the words its length needs sit in LDS
 //                    (fcl::Pats, 10.6 KiB at most).  A thread forms its 16 64-bit windows as
@@ -13,18 +13,11 @@
 // Loads: aligned 16-byte words that hold a byte of [buf, buf + n), as in k_find.hip.
 #include "kolm_internal.h"
 #include "findcls_core.h"
+#include "find_tile.h"
 
 namespace kolm {
 
 namespace {
-
-struct DevLd {
-    const u8* buf;
-    __device__ __forceinline__ fnd::Word operator()(fnd::i64 off) const {
-        const uint4 v = *reinterpret_cast<const uint4*>(buf + off);
-        return fnd::Word{{(u64)v.x | ((u64)v.y << 32), (u64)v.z | ((u64)v.w << 32)}};
-    }
-};
 
 // T, the prefix words and the lengths; of pattern i < np the ceil(len / 8) words of its row
 __device__ __forceinline__ void load_pats(fcl::Pats& sp, const fcl::Pats* __restrict__ P, u32 np) {
@@ -42,31 +35,12 @@ __global__ __launch_bounds__(fnd::WG) void k_findcls_count(const u8* __restrict_
                                                            const fcl::Pats* __restrict__ P, u32 np, u32 ntiles,
                                                            u32* __restrict__ cnt) {
     __shared__ fcl::Pats sp;
-    __shared__ u32 s_c[fnd::WG / 64][fnd::MAX_PATTERNS + 1];
     load_pats(sp, P, np);
-    const u32 tile = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 p0 = tile * fnd::TILE + threadIdx.x * fnd::PER;
-    const u32 mis = (u32)(reinterpret_cast<uintptr_t>(buf) & (fnd::WORD - 1));
-    DevLd ld{buf};
+    const u32 tile = blockIdx.x, p0 = ftl::first_pos(tile), mis = ftl::misalign(buf);
+    ftl::DevLd ld{buf};
     u64 w[fnd::PER];
     fnd::windows(ld, mis, p0, n, w);
-    u32 total = 0;
-    for (u32 i = 0; i < np; ++i) {
-        const u32 m = fcl::match_mask(ld, w, mis, p0, lo, shi, n, sp, i);
-        const u32 c = (u32)__popc(m);
-        total += c;
-        const u32 r = wave_reduce(c, OpAddU(), 0u);
-        if (lane == 0) s_c[wave][i] = r;
-    }
-    const u32 rt = wave_reduce(total, OpAddU(), 0u);
-    if (lane == 0) s_c[wave][fnd::MAX_PATTERNS] = rt;
-    __syncthreads();
-    if (threadIdx.x <= np) {
-        const u32 k = threadIdx.x < np ? threadIdx.x : fnd::MAX_PATTERNS;
-        u32 v = 0;
-        for (u32 x = 0; x < fnd::WG / 64; ++x) v += s_c[x][k];
-        cnt[(size_t)threadIdx.x * ntiles + tile] = v;
-    }
+    ftl::tile_count(np, ntiles, tile, cnt, [&](u32 i) { [[clang::always_inline]] return fcl::match_mask(ld, w, mis, p0, lo, shi, n, sp, i); });
 }
 
 __global__ __launch_bounds__(fnd::WG) void k_findcls_emit(const u8* __restrict__ buf, u32 n, u32 lo, u32 shi,
@@ -74,40 +48,13 @@ __global__ __launch_bounds__(fnd::WG) void k_findcls_emit(const u8* __restrict__
                                                           const u64* __restrict__ tscan, u32* __restrict__ out_pos,
                                                           u8* __restrict__ out_which, u32 cap) {
     __shared__ fcl::Pats sp;
-    __shared__ uint16_t s_pm[fnd::MAX_PATTERNS][fnd::WG];
-    __shared__ u32 s_w[fnd::WG / 64];
     load_pats(sp, P, np);
-    const u32 tile = t0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 p0 = tile * fnd::TILE + tid * fnd::PER;
-    const u32 mis = (u32)(reinterpret_cast<uintptr_t>(buf) & (fnd::WORD - 1));
-    DevLd ld{buf};
+    const u32 tile = t0 + blockIdx.x, p0 = ftl::first_pos(tile), mis = ftl::misalign(buf);
+    ftl::DevLd ld{buf};
     u64 w[fnd::PER];
     fnd::windows(ld, mis, p0, n, w);
-    u32 any = 0, c = 0;
-    for (u32 i = 0; i < np; ++i) {
-        const u32 m = fcl::match_mask(ld, w, mis, p0, lo, shi, n, sp, i);
-        s_pm[i][tid] = (uint16_t)m;
-        any |= m;
-        c += (u32)__popc(m);
-    }
-    const u32 incl = wave_incl_scan(c, OpAddU(), 0u);
-    const u32 wtot = (u32)__builtin_amdgcn_readlane((int)incl, 63);
-    if (lane == 0) s_w[wave] = wtot;
-    __syncthreads();
-    u32 slot = (u32)(tscan[tile] - tscan[t0]) + incl - c;
-    for (u32 x = 0; x < wave; ++x) slot += s_w[x];
-    while (any) {  // the thread's own masks: positions ascending, patterns ascending within one
-        const u32 j = (u32)__ffs((int)any) - 1;
-        any &= any - 1;
-        for (u32 i = 0; i < np; ++i)
-            if ((s_pm[i][tid] >> j) & 1u) {
-                if (slot < cap) {
-                    out_pos[slot] = p0 + j;
-                    out_which[slot] = (u8)i;
-                }
-                ++slot;
-            }
-    }
+    ftl::tile_emit(np, tile, t0, tscan, out_pos, out_which, cap,
+                   [&](u32 i) { [[clang::always_inline]] return fcl::match_mask(ld, w, mis, p0, lo, shi, n, sp, i); });
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // Search of a resident buffer for regular expressions on gfx950 (findrx_core.h): every start of up
 // to 16 expressions, compiled to one deterministic automaton, counted and listed in (position,
-// expression) order.  The tile geometry, the count columns, k_find_scan between the two kernels
-// and the record slots are k_find.hip's; ordering is by launch boundaries only: no spinning, no
-// tickets, no atomics.
+// expression) order.  The tile geometry, the count columns and the record slots are the tile
+// skeleton's (find_tile.h), k_find_scan runs between the two kernels; ordering is by launch
+// boundaries only: no spinning, no tickets, no atomics.
 //   k_findrx_count  one workgroup per 4 KiB tile, 256 threads x 16 positions.  The table (dynamic
 //                   LDS: its own padded size, 32 KiB at most, so small automata leave room for
 //                   more workgroups per CU), the class map (256 B) and the tile's stage (4 368 B:
@@ -15,18 +15,11 @@
 // The device image of an automaton: the class map, then the table in whole 16-byte words.
 #include "kolm_internal.h"
 #include "findrx_core.h"
+#include "find_tile.h"
 
 namespace kolm {
 
 namespace {
-
-struct DevLd {
-    const u8* buf;
-    __device__ __forceinline__ fnd::Word operator()(fnd::i64 off) const {
-        const uint4 v = *reinterpret_cast<const uint4*>(buf + off);
-        return fnd::Word{{(u64)v.x | ((u64)v.y << 32), (u64)v.z | ((u64)v.w << 32)}};
-    }
-};
 
 // the automaton and the stage of `tile` into LDS
 __device__ __forceinline__ void load_tile(const u8* __restrict__ buf, u32 n, u32 mis, u32 tile, const u8* __restrict__ img,
@@ -36,7 +29,7 @@ __device__ __forceinline__ void load_tile(const u8* __restrict__ buf, u32 n, u32
     if (tid < frx::MAP / 16) reinterpret_cast<uint4*>(s_cls)[tid] = g[tid];
     for (u32 x = tid; x < words; x += fnd::WG) reinterpret_cast<uint4*>(s_T)[x] = g[frx::MAP / 16 + x];
     __syncthreads();
-    DevLd ld{buf};
+    ftl::DevLd ld{buf};
     for (u32 w = tid; w < frx::STAGE_WORDS; w += fnd::WG) {
         u32 o[4];
         frx::stage_word(ld, mis, tile, w, n, s_cls, o);
@@ -51,29 +44,11 @@ __global__ __launch_bounds__(fnd::WG) void k_findrx_count(const u8* __restrict__
     extern __shared__ __align__(16) uint16_t s_T[];  // frx::padded_entries(nstates, ncls) entries
     __shared__ __align__(16) u8 s_cls[frx::MAP];
     __shared__ __align__(16) u8 s_stage[frx::STAGE_BYTES];
-    __shared__ u32 s_c[fnd::WG / 64][fnd::MAX_PATTERNS + 1];
-    const u32 tile = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 mis = (u32)(reinterpret_cast<uintptr_t>(buf) & (fnd::WORD - 1));
+    const u32 tile = blockIdx.x, mis = ftl::misalign(buf);
     load_tile(buf, n, mis, tile, img, words, s_T, s_cls, s_stage);
-    const u32 p0 = tile * fnd::TILE + threadIdx.x * fnd::PER;
+    const u32 p0 = ftl::first_pos(tile);
     const u8* sc = s_stage + mis + threadIdx.x * fnd::PER;
-    u32 total = 0;
-    for (u32 i = 0; i < np; ++i) {
-        const u32 m = frx::match_mask(s_T, ncls, sc, p0, lo, shi, n, st.s[i]);
-        const u32 c = (u32)__popc(m);
-        total += c;
-        const u32 r = wave_reduce(c, OpAddU(), 0u);
-        if (lane == 0) s_c[wave][i] = r;
-    }
-    const u32 rt = wave_reduce(total, OpAddU(), 0u);
-    if (lane == 0) s_c[wave][fnd::MAX_PATTERNS] = rt;
-    __syncthreads();
-    if (threadIdx.x <= np) {
-        const u32 k = threadIdx.x < np ? threadIdx.x : fnd::MAX_PATTERNS;
-        u32 v = 0;
-        for (u32 x = 0; x < fnd::WG / 64; ++x) v += s_c[x][k];
-        cnt[(size_t)threadIdx.x * ntiles + tile] = v;
-    }
+    ftl::tile_count(np, ntiles, tile, cnt, [&](u32 i) { [[clang::always_inline]] return frx::match_mask(s_T, ncls, sc, p0, lo, shi, n, st.s[i]); });
 }
 
 __global__ __launch_bounds__(fnd::WG) void k_findrx_emit(const u8* __restrict__ buf, u32 n, u32 lo, u32 shi,
@@ -83,38 +58,12 @@ __global__ __launch_bounds__(fnd::WG) void k_findrx_emit(const u8* __restrict__ 
     extern __shared__ __align__(16) uint16_t s_T[];  // frx::padded_entries(nstates, ncls) entries
     __shared__ __align__(16) u8 s_cls[frx::MAP];
     __shared__ __align__(16) u8 s_stage[frx::STAGE_BYTES];
-    __shared__ uint16_t s_pm[fnd::MAX_PATTERNS][fnd::WG];
-    __shared__ u32 s_w[fnd::WG / 64];
-    const u32 tile = t0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 mis = (u32)(reinterpret_cast<uintptr_t>(buf) & (fnd::WORD - 1));
+    const u32 tile = t0 + blockIdx.x, mis = ftl::misalign(buf);
     load_tile(buf, n, mis, tile, img, words, s_T, s_cls, s_stage);
-    const u32 p0 = tile * fnd::TILE + tid * fnd::PER;
-    const u8* sc = s_stage + mis + tid * fnd::PER;
-    u32 any = 0, c = 0;
-    for (u32 i = 0; i < np; ++i) {
-        const u32 m = frx::match_mask(s_T, ncls, sc, p0, lo, shi, n, st.s[i]);
-        s_pm[i][tid] = (uint16_t)m;
-        any |= m;
-        c += (u32)__popc(m);
-    }
-    const u32 incl = wave_incl_scan(c, OpAddU(), 0u);
-    const u32 wtot = (u32)__builtin_amdgcn_readlane((int)incl, 63);
-    if (lane == 0) s_w[wave] = wtot;
-    __syncthreads();
-    u32 slot = (u32)(tscan[tile] - tscan[t0]) + incl - c;
-    for (u32 x = 0; x < wave; ++x) slot += s_w[x];
-    while (any) {  // the thread's own masks: positions ascending, expressions ascending within one
-        const u32 j = (u32)__ffs((int)any) - 1;
-        any &= any - 1;
-        for (u32 i = 0; i < np; ++i)
-            if ((s_pm[i][tid] >> j) & 1u) {
-                if (slot < cap) {
-                    out_pos[slot] = p0 + j;
-                    out_which[slot] = (u8)i;
-                }
-                ++slot;
-            }
-    }
+    const u32 p0 = ftl::first_pos(tile);
+    const u8* sc = s_stage + mis + threadIdx.x * fnd::PER;
+    ftl::tile_emit(np, tile, t0, tscan, out_pos, out_which, cap,
+                   [&](u32 i) { [[clang::always_inline]] return frx::match_mask(s_T, ncls, sc, p0, lo, shi, n, st.s[i]); });
 }
 
 }  // namespace

@@ -24,18 +24,11 @@
 // [word, word + ceil(len / 8)) of an entry: all inside the set's own allocations.
 #include "kolm_internal.h"
 #include "findset_core.h"
+#include "find_tile.h"
 
 namespace kolm {
 
 namespace {
-
-struct DevLd {
-    const u8* buf;
-    __device__ __forceinline__ fnd::Word operator()(fnd::i64 off) const {
-        const uint4 v = *reinterpret_cast<const uint4*>(buf + off);
-        return fnd::Word{{(u64)v.x | ((u64)v.y << 32), (u64)v.z | ((u64)v.w << 32)}};
-    }
-};
 
 __device__ __forceinline__ void load_filter(u32* sf, const fst::Set& S) {
     for (u32 i = threadIdx.x; i < S.filter_words; i += fnd::WG) sf[i] = S.filter[i];
@@ -50,7 +43,7 @@ __global__ __launch_bounds__(fnd::WG) void k_findset_count(const u8* __restrict_
     load_filter(s_filter, S);
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u32 mis = (u32)(reinterpret_cast<uintptr_t>(buf) & (fnd::WORD - 1));
-    DevLd ld{buf};
+    ftl::DevLd ld{buf};
     const u32 tb = blockIdx.x * span, te = tb + span < ntiles ? tb + span : ntiles;
     for (u32 tile = tb; tile < te; ++tile) {
         const u32 p0 = tile * fnd::TILE + threadIdx.x * fnd::PER;
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(fnd::WG) void k_findset_emit(const u8* __restrict__
     load_filter(s_filter, S);
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u32 mis = (u32)(reinterpret_cast<uintptr_t>(buf) & (fnd::WORD - 1));
-    DevLd ld{buf};
+    ftl::DevLd ld{buf};
     const u32 tb = t0 + blockIdx.x * span, te = tb + span < t1 ? tb + span : t1;
     const u64 base = tscan[t0];
     for (u32 tile = tb; tile < te; ++tile) {

@@ -239,16 +239,17 @@ u64 find_stage_bytes() {  // read per call, like KOLM_READ_BYTES
     return v;
 }
 
-// np patterns, pattern i = pats[pat_off[i], pat_off[i + 1]); L = the longest
-int find_check_pats(const char* who, const uint8_t* pats, const uint32_t* pat_off, u32 np, u32* L) {
-    char msg[160];
-    if (np < 1 || np > KOLM_FIND_MAX_PATTERNS) {
-        snprintf(msg, sizeof msg, "%s: %u patterns (1..%u are allowed)", who, np, (u32)KOLM_FIND_MAX_PATTERNS);
+// A pattern list: np in 1..max_np patterns, pattern i = the units [pat_off[i], pat_off[i + 1]) of
+// `pats` ("bytes" or "positions"), none empty, none longer than KOLM_FIND_MAX_LEN.  L (optional) = the longest.
+int check_pat_list(const char* who, const void* pats, const uint32_t* pat_off, u32 np, u32 max_np, const char* unit, u32* L) {
+    char msg[200];
+    if (np < 1 || np > max_np) {
+        snprintf(msg, sizeof msg, "%s: %u patterns (1..%u are allowed)", who, np, max_np);
         set_err(msg);
         return KOLM_EARG;
     }
     if (!pats || !pat_off) return KOLM_EARG;
-    *L = 0;
+    u32 longest = 0;
     for (u32 i = 0; i < np; ++i) {
         if (pat_off[i + 1] <= pat_off[i]) {
             snprintf(msg, sizeof msg, "%s: pattern %u is empty", who, i);
@@ -257,20 +258,50 @@ int find_check_pats(const char* who, const uint8_t* pats, const uint32_t* pat_of
         }
         const u32 len = pat_off[i + 1] - pat_off[i];
         if (len > KOLM_FIND_MAX_LEN) {
-            snprintf(msg, sizeof msg, "%s: pattern %u has %u bytes (at most %u)", who, i, len, (u32)KOLM_FIND_MAX_LEN);
+            snprintf(msg, sizeof msg, "%s: pattern %u has %u %s (at most %u)", who, i, len, unit, (u32)KOLM_FIND_MAX_LEN);
             set_err(msg);
             return KOLM_EARG;
         }
-        *L = std::max(*L, len);
+        longest = std::max(longest, len);
     }
+    if (L) *L = longest;
     return KOLM_OK;
 }
 
-const fnd::Pats* find_upload_pats(kolm_ctx* c, const uint8_t* pats, const uint32_t* pat_off, u32 np, fnd::Pats& hp) {
-    fnd::make_pats(pats, pat_off, np, hp);
-    fnd::Pats* dp = c->get<fnd::Pats>("fd_pats", 1);
-    KOLM_HIP_CHECK(hipMemcpyAsync(dp, &hp, sizeof hp, hipMemcpyHostToDevice, c->stream));
-    return dp;
+// The three searches that share k_find.hip's tile skeleton differ, on the host, in a variant object:
+//   np, L                      the patterns of the call and the longest match (the hold-back)
+//   count_name, emit_name      the kernels' names for the timing scopes
+//   upload(c)                  the call's tables to the device, on c->stream
+//   count(buf, n, lo, shi, cnt, s), emit(buf, n, lo, shi, t0, t1, tscan, dpos, dwhich, slots, s)
+//                              the two launches around launch_find_scan
+// Each is filled by its own check (find_check_pats, findcls_check_pats, findrx_check), which launches nothing.
+
+// np patterns, pattern i = pats[pat_off[i], pat_off[i + 1])
+struct LitSearch {
+    static constexpr const char *count_name = "k_find_count", *emit_name = "k_find_emit";
+    const uint8_t* pats = nullptr;
+    const uint32_t* pat_off = nullptr;
+    u32 np = 0, L = 0;
+    fnd::Pats hp;
+    const fnd::Pats* dP = nullptr;
+    void upload(kolm_ctx* c) {
+        fnd::make_pats(pats, pat_off, np, hp);
+        fnd::Pats* d = c->get<fnd::Pats>("fd_pats", 1);
+        KOLM_HIP_CHECK(hipMemcpyAsync(d, &hp, sizeof hp, hipMemcpyHostToDevice, c->stream));
+        dP = d;
+    }
+    void count(const u8* buf, u32 n, u32 lo, u32 shi, u32* cnt, hipStream_t s) const {
+        launch_find_count(buf, n, lo, shi, dP, np, cnt, s);
+    }
+    void emit(const u8* buf, u32 n, u32 lo, u32 shi, u32 t0, u32 t1, const u64* tscan, u32* dpos, u8* dwhich, u32 slots,
+              hipStream_t s) const {
+        launch_find_emit(buf, n, lo, shi, dP, np, t0, t1, tscan, dpos, dwhich, slots, s);
+    }
+};
+
+int find_check_pats(const char* who, const uint8_t* pats, const uint32_t* pat_off, u32 np, LitSearch& v) {
+    v.pats = pats, v.pat_off = pat_off, v.np = np;
+    return check_pat_list(who, pats, pat_off, np, KOLM_FIND_MAX_PATTERNS, "bytes", &v.L);
 }
 
 // The emit half of a search of one scan buffer, behind its count, scan and totals round trip
@@ -324,13 +355,13 @@ void emit_matches(kolm_ctx* c, u32 ntiles, const u64* tscan, u64 total, u64 held
     }
 }
 
-// One scan buffer buf [0, n) on c->stream: count, scan, one round trip for the totals, then the
-// emit launches (none when nothing is to be returned).  counts [np] accumulate; (base + position,
+// One scan buffer buf [0, n) on c->stream, for every variant: count, scan, one round trip for the totals,
+// then the emit launches (none when nothing is to be returned).  counts [np] accumulate; (base + position,
 // pattern) are appended to offs / which until `limit` results are held.  more_than: as emit_matches.
-void find_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fnd::Pats* dP, u32 np, u64 base, u64 limit,
-                u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms,
-                u64* more_than = nullptr) {
-    const u32 ntiles = fnd::tiles(n);
+template <class V>
+void find_group(kolm_ctx* c, const V& v, const u8* buf, u32 n, u32 lo, u32 shi, u64 base, u64 limit, u64* counts,
+                std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms, u64* more_than = nullptr) {
+    const u32 ntiles = fnd::tiles(n), np = v.np;
     if (!ntiles) return;
     hipStream_t s = c->stream;
     u32* cnt = c->get<u32>("fd_cnt", (size_t)(np + 1) * ntiles);
@@ -338,8 +369,8 @@ void find_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fnd::P
     u64* tscan = c->get<u64>("fd_scan", (size_t)ntiles + 1);
     KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
     {
-        TScope t(c, KOLM_KT_EMIT, "k_find_count", n);
-        launch_find_count(buf, n, lo, shi, dP, np, cnt, s);
+        TScope t(c, KOLM_KT_EMIT, V::count_name, n);
+        v.count(buf, n, lo, shi, cnt, s);
     }
     {
         TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)(np + 1) * ntiles);
@@ -363,8 +394,8 @@ void find_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fnd::P
             dwhich = c->get<u8>("fd_which", slots);
         },
         [&](u32 t0, u32 t1, u64 recs, u32 slots) {
-            TScope t(c, KOLM_KT_EMIT, "k_find_emit", (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
-            launch_find_emit(buf, n, lo, shi, dP, np, t0, t1, tscan, dpos, dwhich, slots, s);
+            TScope t(c, KOLM_KT_EMIT, V::emit_name, (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
+            v.emit(buf, n, lo, shi, t0, t1, tscan, dpos, dwhich, slots, s);
         },
         [&](u64 take) {
             hpos.resize(take), hwhich.resize(take);
@@ -427,33 +458,33 @@ int find_over_groups(kolm_reader* r, const RangePlan& p, u64 lo, u64 hi, u32 L, 
 
 // ---- class patterns (findcls_core.h, k_findcls.hip) ----
 
-// np class patterns, pattern i = the 32-byte bitmaps [pat_off[i], pat_off[i + 1]); L = the longest.
-// Classifies and deduplicates the classes into hp (no launch yet).
-int findcls_check_pats(const char* who, const uint8_t* bitmaps, const uint32_t* pat_off, u32 np, u32* L, fcl::Pats& hp) {
-    char msg[200];
-    if (np < 1 || np > KOLM_FIND_MAX_PATTERNS) {
-        snprintf(msg, sizeof msg, "%s: %u patterns (1..%u are allowed)", who, np, (u32)KOLM_FIND_MAX_PATTERNS);
-        set_err(msg);
-        return KOLM_EARG;
+// np class patterns, pattern i = the 32-byte bitmaps [pat_off[i], pat_off[i + 1])
+struct ClsSearch {
+    static constexpr const char *count_name = "k_findcls_count", *emit_name = "k_findcls_emit";
+    u32 np = 0, L = 0;
+    fcl::Pats hp;
+    const fcl::Pats* dP = nullptr;
+    void upload(kolm_ctx* c) {
+        fcl::Pats* d = c->get<fcl::Pats>("fc_pats", 1);
+        KOLM_HIP_CHECK(hipMemcpyAsync(d, &hp, sizeof hp, hipMemcpyHostToDevice, c->stream));
+        dP = d;
     }
-    if (!bitmaps || !pat_off) return KOLM_EARG;
-    *L = 0;
-    for (u32 i = 0; i < np; ++i) {
-        if (pat_off[i + 1] <= pat_off[i]) {
-            snprintf(msg, sizeof msg, "%s: pattern %u is empty", who, i);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        const u32 len = pat_off[i + 1] - pat_off[i];
-        if (len > KOLM_FIND_MAX_LEN) {
-            snprintf(msg, sizeof msg, "%s: pattern %u has %u positions (at most %u)", who, i, len, (u32)KOLM_FIND_MAX_LEN);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        *L = std::max(*L, len);
+    void count(const u8* buf, u32 n, u32 lo, u32 shi, u32* cnt, hipStream_t s) const {
+        launch_findcls_count(buf, n, lo, shi, dP, np, cnt, s);
     }
+    void emit(const u8* buf, u32 n, u32 lo, u32 shi, u32 t0, u32 t1, const u64* tscan, u32* dpos, u8* dwhich, u32 slots,
+              hipStream_t s) const {
+        launch_findcls_emit(buf, n, lo, shi, dP, np, t0, t1, tscan, dpos, dwhich, slots, s);
+    }
+};
+
+// Classifies and deduplicates the classes into v.hp (no launch yet).
+int findcls_check_pats(const char* who, const uint8_t* bitmaps, const uint32_t* pat_off, u32 np, ClsSearch& v) {
+    v.np = np;
+    if (int rc = check_pat_list(who, bitmaps, pat_off, np, KOLM_FIND_MAX_PATTERNS, "positions", &v.L)) return rc;
     u32 ntab = 0, bad_pat = 0, bad_pos = 0;
-    if (!fcl::make_pats(bitmaps, pat_off, np, hp, &ntab, &bad_pat, &bad_pos)) {
+    if (!fcl::make_pats(bitmaps, pat_off, np, v.hp, &ntab, &bad_pat, &bad_pos)) {
+        char msg[200];
         snprintf(msg, sizeof msg,
                  "%s: position %u of pattern %u is distinct table class %u of the call (at most %u classes that are no "
                  "masked equality)",
@@ -464,74 +495,32 @@ int findcls_check_pats(const char* who, const uint8_t* bitmaps, const uint32_t* 
     return KOLM_OK;
 }
 
-const fcl::Pats* findcls_upload_pats(kolm_ctx* c, const fcl::Pats& hp) {
-    fcl::Pats* dp = c->get<fcl::Pats>("fc_pats", 1);
-    KOLM_HIP_CHECK(hipMemcpyAsync(dp, &hp, sizeof hp, hipMemcpyHostToDevice, c->stream));
-    return dp;
-}
-
-// find_group for class patterns: the same scratch, scan and emit loop around the class kernels
-void findcls_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const fcl::Pats* dP, u32 np, u64 base, u64 limit,
-                   u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms,
-                   u64* more_than = nullptr) {
-    const u32 ntiles = fnd::tiles(n);
-    if (!ntiles) return;
-    hipStream_t s = c->stream;
-    u32* cnt = c->get<u32>("fd_cnt", (size_t)(np + 1) * ntiles);
-    u64* tot = c->get<u64>("fd_tot", fnd::MAX_PATTERNS + 1);
-    u64* tscan = c->get<u64>("fd_scan", (size_t)ntiles + 1);
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_findcls_count", n);
-        launch_findcls_count(buf, n, lo, shi, dP, np, cnt, s);
-    }
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)(np + 1) * ntiles);
-        launch_find_scan(cnt, ntiles, np, tot, tscan, s);
-    }
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
-    u64 htot[fnd::MAX_PATTERNS + 1] = {};
-    KOLM_HIP_CHECK(hipMemcpyAsync(htot, tot, sizeof(u64) * (np + 1), hipMemcpyDeviceToHost, s));
-    c->sync();
-    ms += ev_ms(c->ev[6], c->ev[7]);
-    for (u32 i = 0; i < np; ++i) counts[i] += htot[i];
-    const u64 cap = std::min<u64>(fnd::stage_records(find_stage_bytes(), np), 0xFFFFFFFFull);
-    u32* dpos = nullptr;
-    u8* dwhich = nullptr;
-    std::vector<u32> hpos;
-    std::vector<u8> hwhich;
-    emit_matches(
-        c, ntiles, tscan, htot[np], offs.size(), limit, cap, more_than, launches, ms,
-        [&](u64 slots) {
-            dpos = c->get<u32>("fd_pos", slots);
-            dwhich = c->get<u8>("fd_which", slots);
-        },
-        [&](u32 t0, u32 t1, u64 recs, u32 slots) {
-            TScope t(c, KOLM_KT_EMIT, "k_findcls_emit", (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
-            launch_findcls_emit(buf, n, lo, shi, dP, np, t0, t1, tscan, dpos, dwhich, slots, s);
-        },
-        [&](u64 take) {
-            hpos.resize(take), hwhich.resize(take);
-            KOLM_HIP_CHECK(hipMemcpyAsync(hpos.data(), dpos, sizeof(u32) * take, hipMemcpyDeviceToHost, s));
-            KOLM_HIP_CHECK(hipMemcpyAsync(hwhich.data(), dwhich, take, hipMemcpyDeviceToHost, s));
-            c->sync();
-            for (u64 k = 0; k < take; ++k) offs.push_back(base + hpos[k]);
-            which.insert(which.end(), hwhich.begin(), hwhich.end());
-        });
-}
-
 // ---- regular expressions (findrx_core.h, k_findrx.hip) ----
 
 // The automaton of a call, checked (frx::validate) and laid out as the kernels read it.
-struct RxCall {
+struct RxSearch {
+    static constexpr const char *count_name = "k_findrx_count", *emit_name = "k_findrx_emit";
     std::vector<u8> img;  // the class map, then the table in whole 16-byte words
     frx::Starts st{};
     u32 nstates = 0, ncls = 0, np = 0;
     u32 L = 0;  // the hold-back, from the table itself
+    const u8* dimg = nullptr;
+    void upload(kolm_ctx* c) {
+        u8* d = c->get<u8>("rx_img", img.size());
+        KOLM_HIP_CHECK(hipMemcpyAsync(d, img.data(), img.size(), hipMemcpyHostToDevice, c->stream));
+        dimg = d;
+    }
+    void count(const u8* buf, u32 n, u32 lo, u32 shi, u32* cnt, hipStream_t s) const {
+        launch_findrx_count(buf, n, lo, shi, dimg, nstates, ncls, st, np, cnt, s);
+    }
+    void emit(const u8* buf, u32 n, u32 lo, u32 shi, u32 t0, u32 t1, const u64* tscan, u32* dpos, u8* dwhich, u32 slots,
+              hipStream_t s) const {
+        launch_findrx_emit(buf, n, lo, shi, dimg, nstates, ncls, st, np, t0, t1, tscan, dpos, dwhich, slots, s);
+    }
 };
 
 int findrx_check(const char* who, const uint8_t* cls_map, const uint16_t* table, u32 nstates, u32 ncls, const uint16_t* starts,
-                 u32 np, RxCall& rx) {
+                 u32 np, RxSearch& rx) {
     char why[200], msg[280];
     if (frx::validate(cls_map, table, nstates, ncls, starts, np, why, sizeof why)) {
         snprintf(msg, sizeof msg, "%s: %s", who, why);
@@ -548,76 +537,14 @@ int findrx_check(const char* who, const uint8_t* cls_map, const uint16_t* table,
     return KOLM_OK;
 }
 
-const u8* findrx_upload(kolm_ctx* c, const RxCall& rx) {
-    u8* d = c->get<u8>("rx_img", rx.img.size());
-    KOLM_HIP_CHECK(hipMemcpyAsync(d, rx.img.data(), rx.img.size(), hipMemcpyHostToDevice, c->stream));
-    return d;
-}
-
-// find_group for regular expressions: the same scratch, scan and emit loop around the DFA kernels
-void findrx_group(kolm_ctx* c, const u8* buf, u32 n, u32 lo, u32 shi, const u8* img, const RxCall& rx, u64 base, u64 limit,
-                  u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32& launches, double& ms,
-                  u64* more_than = nullptr) {
-    const u32 ntiles = fnd::tiles(n), np = rx.np;
-    if (!ntiles) return;
-    hipStream_t s = c->stream;
-    u32* cnt = c->get<u32>("fd_cnt", (size_t)(np + 1) * ntiles);
-    u64* tot = c->get<u64>("fd_tot", fnd::MAX_PATTERNS + 1);
-    u64* tscan = c->get<u64>("fd_scan", (size_t)ntiles + 1);
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[6], s));
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_findrx_count", n);
-        launch_findrx_count(buf, n, lo, shi, img, rx.nstates, rx.ncls, rx.st, np, cnt, s);
-    }
-    {
-        TScope t(c, KOLM_KT_EMIT, "k_find_scan", sizeof(u32) * (u64)(np + 1) * ntiles);
-        launch_find_scan(cnt, ntiles, np, tot, tscan, s);
-    }
-    KOLM_HIP_CHECK(hipEventRecord(c->ev[7], s));
-    u64 htot[fnd::MAX_PATTERNS + 1] = {};
-    KOLM_HIP_CHECK(hipMemcpyAsync(htot, tot, sizeof(u64) * (np + 1), hipMemcpyDeviceToHost, s));
-    c->sync();
-    ms += ev_ms(c->ev[6], c->ev[7]);
-    for (u32 i = 0; i < np; ++i) counts[i] += htot[i];
-    const u64 cap = std::min<u64>(fnd::stage_records(find_stage_bytes(), np), 0xFFFFFFFFull);
-    u32* dpos = nullptr;
-    u8* dwhich = nullptr;
-    std::vector<u32> hpos;
-    std::vector<u8> hwhich;
-    emit_matches(
-        c, ntiles, tscan, htot[np], offs.size(), limit, cap, more_than, launches, ms,
-        [&](u64 slots) {
-            dpos = c->get<u32>("fd_pos", slots);
-            dwhich = c->get<u8>("fd_which", slots);
-        },
-        [&](u32 t0, u32 t1, u64 recs, u32 slots) {
-            TScope t(c, KOLM_KT_EMIT, "k_findrx_emit", (u64)(t1 - t0) * fnd::TILE + fnd::REC_BYTES * recs);
-            launch_findrx_emit(buf, n, lo, shi, img, rx.nstates, rx.ncls, rx.st, np, t0, t1, tscan, dpos, dwhich, slots, s);
-        },
-        [&](u64 take) {
-            hpos.resize(take), hwhich.resize(take);
-            KOLM_HIP_CHECK(hipMemcpyAsync(hpos.data(), dpos, sizeof(u32) * take, hipMemcpyDeviceToHost, s));
-            KOLM_HIP_CHECK(hipMemcpyAsync(hwhich.data(), dwhich, take, hipMemcpyDeviceToHost, s));
-            c->sync();
-            for (u64 k = 0; k < take; ++k) offs.push_back(base + hpos[k]);
-            which.insert(which.end(), hwhich.begin(), hwhich.end());
-        });
-}
-
-}  // namespace
-
-extern "C" {
-
-int kolm_find_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t* pats, const uint32_t* pat_off, uint32_t np,
-                     uint64_t max_results, uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap,
-                     uint64_t* nfound, double* ms) {
-    if (ms) *ms = 0.0;
-    if (nfound) *nfound = 0;
-    if (!c || !counts || !nfound) return KOLM_EARG;
-    u32 L = 0;
-    if (int rc = find_check_pats("kolm_find_device", pats, pat_off, np, &L)) return rc;
+// The body of kolm_find_device, kolm_find_classes_device and kolm_find_dfa_device behind the
+// variant's own check: one resident buffer, one find_group.  A refused call launches nothing.
+template <class V>
+int find_device_call(const char* who, kolm_ctx* c, V& v, const void* d_data, u64 n, u64 max_results, u64* counts, u64* offs,
+                     u8* which, u64 cap, u64* nfound, double* ms) {
+    const u32 np = v.np;
     if (n >= (1ull << 31)) {
-        set_err("kolm_find_device: the buffer must be smaller than 2^31 bytes");
+        set_err(std::string(who) + ": the buffer must be smaller than 2^31 bytes");
         return KOLM_EARG;
     }
     if ((n && !d_data) || (cap && (!offs || (!which && np > 1)))) return KOLM_EARG;
@@ -628,20 +555,18 @@ int kolm_find_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t*
         KOLM_HIP_CHECK(hipSetDevice(c->device));
         c->timing_reset();
         c->active = c->stream;
-        fnd::Pats hp;
-        const fnd::Pats* dP = find_upload_pats(c, pats, pat_off, np, hp);
+        v.upload(c);
         std::vector<u64> o;
         std::vector<u8> w;
         u32 launches = 0;
         double t = 0.0;
         u64 more = cap;
-        find_group(c, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, dP, np, 0, max_results, counts, o, w, launches, t,
-                   &more);
+        find_group(c, v, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, 0, max_results, counts, o, w, launches, t, &more);
         if (c->timing) c->timing_collect_tail(0, nullptr);
         if (ms) *ms = t;
         if (more > cap) {
             *nfound = more;
-            set_err("kolm_find_device: result capacity too small");
+            set_err(std::string(who) + ": result capacity too small");
             return KOLM_ECAP;
         }
         *nfound = o.size();
@@ -651,18 +576,17 @@ int kolm_find_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t*
     });
 }
 
-int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, uint64_t lo, uint64_t hi,
-                     uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
-    if (stats) *stats = kolm_find_stats{};
-    if (nfound) *nfound = 0;
-    if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
-    // every argument check before the first launch: the patterns, the window, the selected blocks
-    u32 L = 0;
-    if (int rc = find_check_pats("kolm_reader_find", pats, pat_off, np, &L)) return rc;
+// The body of kolm_reader_find, kolm_reader_find_classes and kolm_reader_find_dfa behind the
+// variant's own check.  Every remaining check (the window, the selected blocks) precedes the first
+// launch; no results leave a failed call.
+template <class V>
+int reader_find_call(const char* who, kolm_reader* r, V& v, u64 lo, u64 hi, u64 max_results, u64* counts, u64* nfound,
+                     kolm_find_stats* stats) {
+    const u32 np = v.np;
     RangePlan p;
     kolm_find_stats st{};
     st.patterns = np;
-    if (int rc = find_plan("kolm_reader_find", r, lo, hi, p, st)) return rc;
+    if (int rc = find_plan(who, r, lo, hi, p, st)) return rc;
     for (u32 i = 0; i < np; ++i) counts[i] = 0;
     kolm_ctx* c = r->c;
     std::vector<u64> offs;
@@ -672,17 +596,16 @@ int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_of
         r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
         if (p.sel.empty()) return KOLM_OK;
         ReaderCall::enter(c);
-        fnd::Pats hp;
-        const fnd::Pats* dP = find_upload_pats(c, pats, pat_off, np, hp);
-        if (int e = find_over_groups(r, p, lo, hi, L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
-                find_group(c, buf, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which, st.emit_launches,
+        v.upload(c);
+        if (int e = find_over_groups(r, p, lo, hi, v.L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
+                find_group(c, v, buf, gs.n, gs.lo, gs.shi, gs.start, max_results, counts, offs, which, st.emit_launches,
                            st.ms_find);
             }))
             return e;
         if (c->timing) c->timing_collect_tail(0, nullptr);
         return KOLM_OK;
     });
-    if (rc) {  // no results leave a failed call
+    if (rc) {
         for (u32 i = 0; i < np; ++i) counts[i] = 0;
         if (stats) *stats = st;
         return rc;
@@ -696,6 +619,31 @@ int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_of
     }
     if (stats) *stats = st;
     return KOLM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kolm_find_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t* pats, const uint32_t* pat_off, uint32_t np,
+                     uint64_t max_results, uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap,
+                     uint64_t* nfound, double* ms) {
+    if (ms) *ms = 0.0;
+    if (nfound) *nfound = 0;
+    if (!c || !counts || !nfound) return KOLM_EARG;
+    LitSearch v;
+    if (int rc = find_check_pats("kolm_find_device", pats, pat_off, np, v)) return rc;
+    return find_device_call("kolm_find_device", c, v, d_data, n, max_results, counts, offs, which, cap, nfound, ms);
+}
+
+int kolm_reader_find(kolm_reader* r, const uint8_t* pats, const uint32_t* pat_off, uint32_t np, uint64_t lo, uint64_t hi,
+                     uint64_t max_results, uint64_t* counts, uint64_t* nfound, kolm_find_stats* stats) {
+    if (stats) *stats = kolm_find_stats{};
+    if (nfound) *nfound = 0;
+    if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
+    LitSearch v;
+    if (int rc = find_check_pats("kolm_reader_find", pats, pat_off, np, v)) return rc;
+    return reader_find_call("kolm_reader_find", r, v, lo, hi, max_results, counts, nfound, stats);
 }
 
 int kolm_reader_find_copy(kolm_reader* r, uint64_t first, uint64_t n, uint64_t* offs, uint8_t* which) {
@@ -717,41 +665,9 @@ int kolm_find_classes_device(kolm_ctx* c, const void* d_data, uint64_t n, const 
     if (ms) *ms = 0.0;
     if (nfound) *nfound = 0;
     if (!c || !counts || !nfound) return KOLM_EARG;
-    u32 L = 0;
-    fcl::Pats hp;
-    if (int rc = findcls_check_pats("kolm_find_classes_device", bitmaps, pat_off, np, &L, hp)) return rc;
-    if (n >= (1ull << 31)) {
-        set_err("kolm_find_classes_device: the buffer must be smaller than 2^31 bytes");
-        return KOLM_EARG;
-    }
-    if ((n && !d_data) || (cap && (!offs || (!which && np > 1)))) return KOLM_EARG;
-    for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    if (n == 0) return KOLM_OK;
-    return guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        c->active = c->stream;
-        const fcl::Pats* dP = findcls_upload_pats(c, hp);
-        std::vector<u64> o;
-        std::vector<u8> w;
-        u32 launches = 0;
-        double t = 0.0;
-        u64 more = cap;
-        findcls_group(c, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, dP, np, 0, max_results, counts, o, w, launches,
-                      t, &more);
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        if (ms) *ms = t;
-        if (more > cap) {
-            *nfound = more;
-            set_err("kolm_find_classes_device: result capacity too small");
-            return KOLM_ECAP;
-        }
-        *nfound = o.size();
-        std::copy(o.begin(), o.end(), offs);
-        if (which) std::copy(w.begin(), w.end(), which);
-        return KOLM_OK;
-    });
+    ClsSearch v;
+    if (int rc = findcls_check_pats("kolm_find_classes_device", bitmaps, pat_off, np, v)) return rc;
+    return find_device_call("kolm_find_classes_device", c, v, d_data, n, max_results, counts, offs, which, cap, nfound, ms);
 }
 
 int kolm_reader_find_classes(kolm_reader* r, const uint8_t* bitmaps, const uint32_t* pat_off, uint32_t np, uint64_t lo,
@@ -759,46 +675,9 @@ int kolm_reader_find_classes(kolm_reader* r, const uint8_t* bitmaps, const uint3
     if (stats) *stats = kolm_find_stats{};
     if (nfound) *nfound = 0;
     if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
-    // every argument check before the first launch: the patterns, the window, the selected blocks
-    u32 L = 0;
-    fcl::Pats hp;
-    if (int rc = findcls_check_pats("kolm_reader_find_classes", bitmaps, pat_off, np, &L, hp)) return rc;
-    RangePlan p;
-    kolm_find_stats st{};
-    st.patterns = np;
-    if (int rc = find_plan("kolm_reader_find_classes", r, lo, hi, p, st)) return rc;
-    for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    kolm_ctx* c = r->c;
-    std::vector<u64> offs;
-    std::vector<u8> which;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
-        if (p.sel.empty()) return KOLM_OK;
-        ReaderCall::enter(c);
-        const fcl::Pats* dP = findcls_upload_pats(c, hp);
-        if (int e = find_over_groups(r, p, lo, hi, L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
-                findcls_group(c, buf, gs.n, gs.lo, gs.shi, dP, np, gs.start, max_results, counts, offs, which,
-                              st.emit_launches, st.ms_find);
-            }))
-            return e;
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        return KOLM_OK;
-    });
-    if (rc) {  // no results leave a failed call
-        for (u32 i = 0; i < np; ++i) counts[i] = 0;
-        if (stats) *stats = st;
-        return rc;
-    }
-    for (u32 i = 0; i < np; ++i) st.matches += counts[i];
-    st.returned = offs.size();
-    *nfound = offs.size();
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.swap(offs), r->f_which.swap(which);
-    }
-    if (stats) *stats = st;
-    return KOLM_OK;
+    ClsSearch v;
+    if (int rc = findcls_check_pats("kolm_reader_find_classes", bitmaps, pat_off, np, v)) return rc;
+    return reader_find_call("kolm_reader_find_classes", r, v, lo, hi, max_results, counts, nfound, stats);
 }
 
 int kolm_find_dfa_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint8_t* cls_map, const uint16_t* table,
@@ -807,40 +686,9 @@ int kolm_find_dfa_device(kolm_ctx* c, const void* d_data, uint64_t n, const uint
     if (ms) *ms = 0.0;
     if (nfound) *nfound = 0;
     if (!c || !counts || !nfound) return KOLM_EARG;
-    RxCall rx;
-    if (int rc = findrx_check("kolm_find_dfa_device", cls_map, table, nstates, ncls, starts, np, rx)) return rc;
-    if (n >= (1ull << 31)) {
-        set_err("kolm_find_dfa_device: the buffer must be smaller than 2^31 bytes");
-        return KOLM_EARG;
-    }
-    if ((n && !d_data) || (cap && (!offs || (!which && np > 1)))) return KOLM_EARG;
-    for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    if (n == 0) return KOLM_OK;
-    return guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        KOLM_HIP_CHECK(hipSetDevice(c->device));
-        c->timing_reset();
-        c->active = c->stream;
-        const u8* img = findrx_upload(c, rx);
-        std::vector<u64> o;
-        std::vector<u8> w;
-        u32 launches = 0;
-        double t = 0.0;
-        u64 more = cap;
-        findrx_group(c, static_cast<const u8*>(d_data), (u32)n, 0, (u32)n, img, rx, 0, max_results, counts, o, w, launches, t,
-                     &more);
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        if (ms) *ms = t;
-        if (more > cap) {
-            *nfound = more;
-            set_err("kolm_find_dfa_device: result capacity too small");
-            return KOLM_ECAP;
-        }
-        *nfound = o.size();
-        std::copy(o.begin(), o.end(), offs);
-        if (which) std::copy(w.begin(), w.end(), which);
-        return KOLM_OK;
-    });
+    RxSearch v;
+    if (int rc = findrx_check("kolm_find_dfa_device", cls_map, table, nstates, ncls, starts, np, v)) return rc;
+    return find_device_call("kolm_find_dfa_device", c, v, d_data, n, max_results, counts, offs, which, cap, nfound, ms);
 }
 
 int kolm_reader_find_dfa(kolm_reader* r, const uint8_t* cls_map, const uint16_t* table, uint32_t nstates, uint32_t ncls,
@@ -849,45 +697,9 @@ int kolm_reader_find_dfa(kolm_reader* r, const uint8_t* cls_map, const uint16_t*
     if (stats) *stats = kolm_find_stats{};
     if (nfound) *nfound = 0;
     if (!r || !r->c || !counts || !nfound) return KOLM_EARG;
-    // every argument check before the first launch: the automaton, the window, the selected blocks
-    RxCall rx;
-    if (int rc = findrx_check("kolm_reader_find_dfa", cls_map, table, nstates, ncls, starts, np, rx)) return rc;
-    RangePlan p;
-    kolm_find_stats st{};
-    st.patterns = np;
-    if (int rc = find_plan("kolm_reader_find_dfa", r, lo, hi, p, st)) return rc;
-    for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    kolm_ctx* c = r->c;
-    std::vector<u64> offs;
-    std::vector<u8> which;
-    int rc = guarded([&] {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.clear(), r->f_which.clear(), r->fs_offs.clear(), r->fs_which.clear();
-        if (p.sel.empty()) return KOLM_OK;
-        ReaderCall::enter(c);
-        const u8* img = findrx_upload(c, rx);
-        if (int e = find_over_groups(r, p, lo, hi, rx.L, st, [&](const u8* buf, const fnd::GroupScan& gs) {
-                findrx_group(c, buf, gs.n, gs.lo, gs.shi, img, rx, gs.start, max_results, counts, offs, which,
-                             st.emit_launches, st.ms_find);
-            }))
-            return e;
-        if (c->timing) c->timing_collect_tail(0, nullptr);
-        return KOLM_OK;
-    });
-    if (rc) {  // no results leave a failed call
-        for (u32 i = 0; i < np; ++i) counts[i] = 0;
-        if (stats) *stats = st;
-        return rc;
-    }
-    for (u32 i = 0; i < np; ++i) st.matches += counts[i];
-    st.returned = offs.size();
-    *nfound = offs.size();
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        r->f_offs.swap(offs), r->f_which.swap(which);
-    }
-    if (stats) *stats = st;
-    return KOLM_OK;
+    RxSearch v;
+    if (int rc = findrx_check("kolm_reader_find_dfa", cls_map, table, nstates, ncls, starts, np, v)) return rc;
+    return reader_find_call("kolm_reader_find_dfa", r, v, lo, hi, max_results, counts, nfound, stats);
 }
 
 }  // extern "C"
@@ -976,27 +788,9 @@ int kolm_patset_create(kolm_ctx* c, const uint8_t* pats, const uint32_t* pat_off
     *out = nullptr;
     if (!c) c = need_default();
     if (!c) return KOLM_ENOINIT;
+    if (int rc = check_pat_list("kolm_patset_create", pats, pat_off, np, KOLM_FIND_SET_MAX_PATTERNS, "bytes", nullptr))
+        return rc;
     char msg[160];
-    if (np < 1 || np > KOLM_FIND_SET_MAX_PATTERNS) {
-        snprintf(msg, sizeof msg, "kolm_patset_create: %u patterns (1..%u are allowed)", np, (u32)KOLM_FIND_SET_MAX_PATTERNS);
-        set_err(msg);
-        return KOLM_EARG;
-    }
-    if (!pats || !pat_off) return KOLM_EARG;
-    for (u32 i = 0; i < np; ++i) {
-        if (pat_off[i + 1] <= pat_off[i]) {
-            snprintf(msg, sizeof msg, "kolm_patset_create: pattern %u is empty", i);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-        const u32 len = pat_off[i + 1] - pat_off[i];
-        if (len > KOLM_FIND_MAX_LEN) {
-            snprintf(msg, sizeof msg, "kolm_patset_create: pattern %u has %u bytes (at most %u)", i, len,
-                     (u32)KOLM_FIND_MAX_LEN);
-            set_err(msg);
-            return KOLM_EARG;
-        }
-    }
     fst::Tables T;
     u32 dup[2] = {0, 0};
     if (!fst::build(pats, pat_off, np, T, dup)) {

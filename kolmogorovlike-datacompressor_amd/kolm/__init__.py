@@ -835,35 +835,50 @@ class Reader:
         n = self._total - offset if size is None or size < 0 else min(int(size), self._total - offset)
         return self.read_many([(offset, n)])[0]
 
+    def _window(self, start, end, limit):
+        """(lo, hi) of data[start:end]: clipped to the data as slice bounds are; a negative start,
+        end or limit raises ValueError."""
+        start, end = int(start), self._total if end is None else int(end)
+        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
+            raise ValueError("start, end and limit must not be negative")
+        return min(start, self._total), min(end, self._total)
+
+    def _search_host(self, lo, hi, limit, npat, hits_of):
+        """A search of data[lo:hi] on the host, for a window with a block the device does not
+        decode: hits_of(data) yields (offset in data, pattern index) of every match of the npat
+        patterns, in any order.  Returns what the device path returns; the stats go to last_find()."""
+        global _last_find
+        data = self._read_host([(lo, hi - lo)])[0]
+        hits, counts = [], [0] * npat
+        for o, i in hits_of(data):
+            hits.append((lo + o, i))
+            counts[i] += 1
+        hits.sort()
+        if limit is not None:
+            hits = hits[:int(limit)]
+        rd = dict(_last_read)
+        _last_find = {"host": True, "patterns": npat, "matches": sum(counts), "returned": len(hits),
+                      "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
+                      "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
+                      "ms_find": 0.0}
+        return [o for o, _ in hits], [i for _, i in hits], counts
+
     def _search(self, patterns, start, end, limit):
         """(offsets, pattern indices, counts) of the patterns in data[start:end]."""
         global _last_find
         h = self._handle()
         pats = _lib.find_patterns(patterns)
-        start, end = int(start), self._total if end is None else int(end)
-        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
-            raise ValueError("start, end and limit must not be negative")
-        lo, hi = min(start, self._total), min(end, self._total)
+        lo, hi = self._window(start, end, limit)
         if lo >= hi:  # nothing to search: no device call
             return [], [], [0] * len(pats)
         if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
-            data = self._read_host([(lo, hi - lo)])[0]
-            hits, counts = [], [0] * len(pats)
-            for i, p in enumerate(pats):
-                o = data.find(p)
-                while o >= 0:
-                    hits.append((lo + o, i))
-                    counts[i] += 1
-                    o = data.find(p, o + 1)
-            hits.sort()
-            if limit is not None:
-                hits = hits[:int(limit)]
-            rd = dict(_last_read)
-            _last_find = {"host": True, "patterns": len(pats), "matches": sum(counts), "returned": len(hits),
-                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
-                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
-                          "ms_find": 0.0}
-            return [o for o, _ in hits], [i for _, i in hits], counts
+            def hits_of(data):
+                for i, p in enumerate(pats):
+                    o = data.find(p)
+                    while o >= 0:
+                        yield o, i
+                        o = data.find(p, o + 1)
+            return self._search_host(lo, hi, limit, len(pats), hits_of)
         offs, which, counts = _lib.reader_find(h, pats, lo, hi, limit)
         _last_find = {}
         return offs, which, counts
@@ -912,28 +927,15 @@ class Reader:
         if classes.table_classes(pats) > classes.MAX_TABLE_CLASSES:
             raise ValueError(f"the patterns hold {classes.table_classes(pats)} distinct classes that are no masked "
                              f"equality (at most {classes.MAX_TABLE_CLASSES})")
-        start, end = int(start), self._total if end is None else int(end)
-        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
-            raise ValueError("start, end and limit must not be negative")
-        lo, hi = min(start, self._total), min(end, self._total)
+        lo, hi = self._window(start, end, limit)
         if lo >= hi:  # nothing to search: no device call
             return [], [], [0] * len(pats)
         if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
-            data = self._read_host([(lo, hi - lo)])[0]
-            hits, counts = [], [0] * len(pats)
-            for i, p in enumerate(pats):  # the lookahead finds overlapping matches too
-                for m in re.finditer(b"(?=(" + p.regex() + b"))", data, re.DOTALL):
-                    hits.append((lo + m.start(), i))
-                    counts[i] += 1
-            hits.sort()
-            if limit is not None:
-                hits = hits[:int(limit)]
-            rd = dict(_last_read)
-            _last_find = {"host": True, "patterns": len(pats), "matches": sum(counts), "returned": len(hits),
-                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
-                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
-                          "ms_find": 0.0}
-            return [o for o, _ in hits], [i for _, i in hits], counts
+            def hits_of(data):
+                for i, p in enumerate(pats):  # the lookahead finds overlapping matches too
+                    for m in re.finditer(b"(?=(" + p.regex() + b"))", data, re.DOTALL):
+                        yield m.start(), i
+            return self._search_host(lo, hi, limit, len(pats), hits_of)
         offs, which, counts = _lib.reader_find_classes(h, [p.bitmaps for p in pats], lo, hi, limit)
         _last_find = {}
         return offs, which, counts
@@ -959,29 +961,16 @@ class Reader:
         global _last_find
         h = self._handle()
         table = regex.table(rxs)  # ValueError: no expression, more than 16, too large an automaton
-        start, end = int(start), self._total if end is None else int(end)
-        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
-            raise ValueError("start, end and limit must not be negative")
-        lo, hi = min(start, self._total), min(end, self._total)
+        lo, hi = self._window(start, end, limit)
         if lo >= hi:  # nothing to search: no device call
             return [], [], [0] * len(rxs)
         if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
-            data = self._read_host([(lo, hi - lo)])[0]
-            hits, counts = [], [0] * len(rxs)
-            for i, r in enumerate(rxs):  # the rule of kolm.h, offset by offset
-                for o in range(len(data)):
-                    if r.host.match(data, o, min(len(data), o + regex.MAX_WALK)) is not None:
-                        hits.append((lo + o, i))
-                        counts[i] += 1
-            hits.sort()
-            if limit is not None:
-                hits = hits[:int(limit)]
-            rd = dict(_last_read)
-            _last_find = {"host": True, "patterns": len(rxs), "matches": sum(counts), "returned": len(hits),
-                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
-                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
-                          "ms_find": 0.0}
-            return [o for o, _ in hits], [i for _, i in hits], counts
+            def hits_of(data):
+                for i, r in enumerate(rxs):  # the rule of kolm.h, offset by offset
+                    for o in range(len(data)):
+                        if r.host.match(data, o, min(len(data), o + regex.MAX_WALK)) is not None:
+                            yield o, i
+            return self._search_host(lo, hi, limit, len(rxs), hits_of)
         offs, which, counts = _lib.reader_find_dfa(h, table, lo, hi, limit)
         _last_find = {}
         return offs, which, counts
@@ -1014,33 +1003,20 @@ class Reader:
                 return self._search_set(tmp, start, end, limit)
         ph = pset._handle()
         pats = pset.patterns
-        start, end = int(start), self._total if end is None else int(end)
-        if start < 0 or end < 0 or (limit is not None and int(limit) < 0):
-            raise ValueError("start, end and limit must not be negative")
-        lo, hi = min(start, self._total), min(end, self._total)
+        lo, hi = self._window(start, end, limit)
         if lo >= hi:  # nothing to search: no device call
             return [], [], [0] * len(pats)
         if self._host_blocks and self._touches_host_block([(lo, hi - lo)]):
-            data = self._read_host([(lo, hi - lo)])[0]
-            by_len: Dict[int, Dict[bytes, int]] = {}
-            for i, p in enumerate(pats):
-                by_len.setdefault(len(p), {})[p] = i
-            hits, counts = [], [0] * len(pats)
-            for ln, table in by_len.items():
-                for o in range(len(data) - ln + 1):
-                    i = table.get(data[o:o + ln])
-                    if i is not None:
-                        hits.append((lo + o, i))
-                        counts[i] += 1
-            hits.sort()
-            if limit is not None:
-                hits = hits[:int(limit)]
-            rd = dict(_last_read)
-            _last_find = {"host": True, "patterns": len(pats), "matches": sum(counts), "returned": len(hits),
-                          "blocks_decoded": rd["blocks_decoded"], "groups": 0, "emit_launches": 0,
-                          "bytes_decoded": rd["bytes_decoded"], "bytes_scanned": hi - lo, "ms_decode": 0.0,
-                          "ms_find": 0.0}
-            return [o for o, _ in hits], [i for _, i in hits], counts
+            def hits_of(data):
+                by_len: Dict[int, Dict[bytes, int]] = {}
+                for i, p in enumerate(pats):
+                    by_len.setdefault(len(p), {})[p] = i
+                for ln, table in by_len.items():
+                    for o in range(len(data) - ln + 1):
+                        i = table.get(data[o:o + ln])
+                        if i is not None:
+                            yield o, i
+            return self._search_host(lo, hi, limit, len(pats), hits_of)
         offs, which, counts = _lib.reader_find_set(h, ph, len(pats), lo, hi, limit)
         _last_find = {}
         return offs, which, counts

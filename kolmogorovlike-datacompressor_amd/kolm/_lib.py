@@ -1358,29 +1358,59 @@ def _pattern_arrays(pats):
     return flat, off
 
 
+def _find_device_call(fn, lead, npat: int, which_dtype, limit, cap=0):
+    """The two-call protocol of a kolm_find_*_device function fn, whose arguments begin with `lead`
+    (the context, the buffer and the variant's patterns).  The first call has room for `cap` results
+    (0: it only counts); KOLM_ECAP names the capacity, and the second call emits.  Returns (offsets,
+    pattern indices as which_dtype, counts of the npat patterns, device ms); the library's argument
+    errors raise ValueError."""
+    counts = np.zeros(max(npat, 1), dtype=np.uint64)
+    nfound, ms = U64(0), ctypes.c_double(0.0)
+    lim = NO_LIMIT if limit is None else int(limit)
+
+    def call(k):
+        offs = np.zeros(max(k, 1), dtype=np.uint64)
+        which = np.zeros(max(k, 1), dtype=which_dtype)
+        rc = fn(*lead, lim, counts.ctypes.data, offs.ctypes.data, which.ctypes.data, k, ctypes.byref(nfound), ctypes.byref(ms))
+        return rc, offs, which
+
+    rc, offs, which = call(int(cap or 0))
+    if rc == -1:
+        raise ValueError(load().kolm_last_error().decode())
+    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
+        rc, offs, which = call(int(nfound.value))
+    check(rc)
+    k = int(nfound.value)
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:npat]], ms.value
+
+
+def _reader_find_call(fn, copy, h, lead, lo: int, hi: int, npat: int, which_dtype, limit):
+    """A kolm_reader_find* function fn with the variant's arguments `lead` behind the reader, then
+    its copy function (kolm_reader_find_copy / _copy32).  Returns (offsets, pattern indices, counts
+    of the npat patterns); the stats go to last_find().  Argument errors raise ValueError, a
+    checksum mismatch KolmChecksumError, and last_find() keeps what it held."""
+    global _last_find
+    counts = np.zeros(max(npat, 1), dtype=np.uint64)
+    nfound = U64(0)
+    st = FindStats()
+    lim = NO_LIMIT if limit is None else int(limit)
+    _read_check(fn(h, *lead, lo, hi, lim, counts.ctypes.data, ctypes.byref(nfound), ctypes.byref(st)))
+    k = int(nfound.value)
+    offs = np.zeros(max(k, 1), dtype=np.uint64)
+    which = np.zeros(max(k, 1), dtype=which_dtype)
+    check(copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
+    _last_find = st.as_dict()
+    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:npat]]
+
+
 def find_device(ctx, dptr: int, n: int, patterns, limit=None):
     """kolm_find_device over the n bytes at the device address dptr.  Returns (offsets,
     pattern indices, counts per pattern, device ms); the patterns are passed as given (the
     library's argument errors raise ValueError)."""
     pats = list(patterns)
     flat, off = _pattern_arrays(pats)
-    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
-    nfound, ms = U64(0), ctypes.c_double(0.0)
-    lim = NO_LIMIT if limit is None else int(limit)
-    L = load()
-    rc = L.kolm_find_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim, counts.ctypes.data, None,
-                            None, 0, ctypes.byref(nfound), ctypes.byref(ms))
-    if rc == -1:
-        raise ValueError(L.kolm_last_error().decode())
-    k = int(nfound.value)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint8)
-    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
-        rc = L.kolm_find_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim, counts.ctypes.data,
-                                offs.ctypes.data, which.ctypes.data, k, ctypes.byref(nfound), ctypes.byref(ms))
-    check(rc)
-    k = int(nfound.value)
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]], ms.value
+    lead = (ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats))
+    return _find_device_call(load().kolm_find_device, lead, len(pats), np.uint8, limit)
 
 
 def find_bytes(data, patterns, limit=None, device: int = None, data_offset: int = 0):
@@ -1392,21 +1422,11 @@ def reader_find(h, patterns, lo: int, hi: int, limit=None):
     """kolm_reader_find + kolm_reader_find_copy.  Returns (offsets, pattern indices, counts per
     pattern); the stats go to last_find().  Argument errors raise ValueError, a checksum
     mismatch KolmChecksumError, and last_find() keeps what it held."""
-    global _last_find
     pats = list(patterns)
     flat, off = _pattern_arrays(pats)
-    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
-    nfound = U64(0)
-    st = FindStats()
-    lim = NO_LIMIT if limit is None else int(limit)
-    _read_check(load().kolm_reader_find(h, flat.ctypes.data, off.ctypes.data, len(pats), lo, hi, lim, counts.ctypes.data,
-                                        ctypes.byref(nfound), ctypes.byref(st)))
-    k = int(nfound.value)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint8)
-    check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
-    _last_find = st.as_dict()
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]]
+    L = load()
+    return _reader_find_call(L.kolm_reader_find, L.kolm_reader_find_copy, h, (flat.ctypes.data, off.ctypes.data, len(pats)),
+                             lo, hi, len(pats), np.uint8, limit)
 
 
 # ---- class patterns (kolm_find_classes_device, kolm_reader_find_classes) --------------------
@@ -1424,24 +1444,8 @@ def find_classes_device(ctx, dptr: int, n: int, bitmaps, limit=None):
     find_device returns.  The patterns are passed as given."""
     pats = list(bitmaps)
     flat, off = _class_arrays(pats)
-    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
-    nfound, ms = U64(0), ctypes.c_double(0.0)
-    lim = NO_LIMIT if limit is None else int(limit)
-    L = load()
-    rc = L.kolm_find_classes_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim, counts.ctypes.data,
-                                    None, None, 0, ctypes.byref(nfound), ctypes.byref(ms))
-    if rc == -1:
-        raise ValueError(L.kolm_last_error().decode())
-    k = int(nfound.value)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint8)
-    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
-        rc = L.kolm_find_classes_device(ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats), lim,
-                                        counts.ctypes.data, offs.ctypes.data, which.ctypes.data, k, ctypes.byref(nfound),
-                                        ctypes.byref(ms))
-    check(rc)
-    k = int(nfound.value)
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]], ms.value
+    lead = (ctx, dptr, n, flat.ctypes.data, off.ctypes.data, len(pats))
+    return _find_device_call(load().kolm_find_classes_device, lead, len(pats), np.uint8, limit)
 
 
 def find_classes_bytes(data, bitmaps, limit=None, device: int = None, data_offset: int = 0):
@@ -1451,21 +1455,11 @@ def find_classes_bytes(data, bitmaps, limit=None, device: int = None, data_offse
 
 def reader_find_classes(h, bitmaps, lo: int, hi: int, limit=None):
     """kolm_reader_find_classes + kolm_reader_find_copy; returns and raises as reader_find."""
-    global _last_find
     pats = list(bitmaps)
     flat, off = _class_arrays(pats)
-    counts = np.zeros(max(len(pats), 1), dtype=np.uint64)
-    nfound = U64(0)
-    st = FindStats()
-    lim = NO_LIMIT if limit is None else int(limit)
-    _read_check(load().kolm_reader_find_classes(h, flat.ctypes.data, off.ctypes.data, len(pats), lo, hi, lim,
-                                                counts.ctypes.data, ctypes.byref(nfound), ctypes.byref(st)))
-    k = int(nfound.value)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint8)
-    check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
-    _last_find = st.as_dict()
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:len(pats)]]
+    L = load()
+    return _reader_find_call(L.kolm_reader_find_classes, L.kolm_reader_find_copy, h,
+                             (flat.ctypes.data, off.ctypes.data, len(pats)), lo, hi, len(pats), np.uint8, limit)
 
 
 # ---- regular expressions (kolm_find_dfa_device, kolm_reader_find_dfa) -----------------------
@@ -1485,23 +1479,8 @@ def find_dfa_device(ctx, dptr: int, n: int, table, limit=None):
     """kolm_find_dfa_device over the n bytes at the device address dptr; returns what find_device
     returns.  The automaton is passed as given."""
     cls, T, starts, ne = _dfa_arrays(table)
-    counts = np.zeros(max(ne, 1), dtype=np.uint64)
-    nfound, ms = U64(0), ctypes.c_double(0.0)
-    lim = NO_LIMIT if limit is None else int(limit)
-    L = load()
-    args = (cls.ctypes.data, T.ctypes.data, T.shape[0], T.shape[1], starts.ctypes.data, ne, lim, counts.ctypes.data)
-    rc = L.kolm_find_dfa_device(ctx, dptr, n, *args, None, None, 0, ctypes.byref(nfound), ctypes.byref(ms))
-    if rc == -1:
-        raise ValueError(L.kolm_last_error().decode())
-    k = int(nfound.value)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint8)
-    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
-        rc = L.kolm_find_dfa_device(ctx, dptr, n, *args, offs.ctypes.data, which.ctypes.data, k, ctypes.byref(nfound),
-                                    ctypes.byref(ms))
-    check(rc)
-    k = int(nfound.value)
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:ne]], ms.value
+    lead = (ctx, dptr, n, cls.ctypes.data, T.ctypes.data, T.shape[0], T.shape[1], starts.ctypes.data, ne)
+    return _find_device_call(load().kolm_find_dfa_device, lead, ne, np.uint8, limit)
 
 
 def find_dfa_bytes(data, table, limit=None, device: int = None, data_offset: int = 0):
@@ -1511,20 +1490,11 @@ def find_dfa_bytes(data, table, limit=None, device: int = None, data_offset: int
 
 def reader_find_dfa(h, table, lo: int, hi: int, limit=None):
     """kolm_reader_find_dfa + kolm_reader_find_copy; returns and raises as reader_find."""
-    global _last_find
     cls, T, starts, ne = _dfa_arrays(table)
-    counts = np.zeros(max(ne, 1), dtype=np.uint64)
-    nfound = U64(0)
-    st = FindStats()
-    lim = NO_LIMIT if limit is None else int(limit)
-    _read_check(load().kolm_reader_find_dfa(h, cls.ctypes.data, T.ctypes.data, T.shape[0], T.shape[1], starts.ctypes.data, ne,
-                                            lo, hi, lim, counts.ctypes.data, ctypes.byref(nfound), ctypes.byref(st)))
-    k = int(nfound.value)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint8)
-    check(load().kolm_reader_find_copy(h, 0, k, offs.ctypes.data, which.ctypes.data))
-    _last_find = st.as_dict()
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:ne]]
+    L = load()
+    return _reader_find_call(L.kolm_reader_find_dfa, L.kolm_reader_find_copy, h,
+                             (cls.ctypes.data, T.ctypes.data, T.shape[0], T.shape[1], starts.ctypes.data, ne), lo, hi, ne,
+                             np.uint8, limit)
 
 
 # ---- pattern sets (kolm_patset_create, kolm_find_set_device, kolm_reader_find_set) ---------
@@ -1576,25 +1546,7 @@ def find_set_device(ctx, dptr: int, n: int, pset, limit=None, cap=None):
     L = load()
     info = PatsetInfo()
     check(L.kolm_patset_info(pset, ctypes.byref(info)))
-    counts = np.zeros(info.np, dtype=np.uint64)
-    nfound, ms = U64(0), ctypes.c_double(0.0)
-    lim = NO_LIMIT if limit is None else int(limit)
-    k = int(cap or 0)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint32)
-    rc = L.kolm_find_set_device(ctx, dptr, n, pset, lim, counts.ctypes.data, offs.ctypes.data, which.ctypes.data, k,
-                                ctypes.byref(nfound), ctypes.byref(ms))
-    if rc == -1:
-        raise ValueError(L.kolm_last_error().decode())
-    if rc == KOLM_ECAP:  # the capacity is known now: the second call emits
-        k = int(nfound.value)
-        offs = np.zeros(max(k, 1), dtype=np.uint64)
-        which = np.zeros(max(k, 1), dtype=np.uint32)
-        rc = L.kolm_find_set_device(ctx, dptr, n, pset, lim, counts.ctypes.data, offs.ctypes.data, which.ctypes.data, k,
-                                    ctypes.byref(nfound), ctypes.byref(ms))
-    check(rc)
-    k = int(nfound.value)
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts], ms.value
+    return _find_device_call(L.kolm_find_set_device, (ctx, dptr, n, pset), info.np, np.uint32, limit, cap)
 
 
 def find_set_bytes(data, patterns, limit=None, data_offset: int = 0, device: int = None, cap=None):
@@ -1612,18 +1564,8 @@ def find_set_bytes(data, patterns, limit=None, data_offset: int = 0, device: int
 def reader_find_set(h, pset, np_: int, lo: int, hi: int, limit=None):
     """kolm_reader_find_set + kolm_reader_find_copy32.  Returns (offsets, pattern indices, counts
     per pattern); the stats go to last_find().  Errors as reader_find."""
-    global _last_find
-    counts = np.zeros(max(np_, 1), dtype=np.uint64)
-    nfound = U64(0)
-    st = FindStats()
-    lim = NO_LIMIT if limit is None else int(limit)
-    _read_check(load().kolm_reader_find_set(h, pset, lo, hi, lim, counts.ctypes.data, ctypes.byref(nfound), ctypes.byref(st)))
-    k = int(nfound.value)
-    offs = np.zeros(max(k, 1), dtype=np.uint64)
-    which = np.zeros(max(k, 1), dtype=np.uint32)
-    check(load().kolm_reader_find_copy32(h, 0, k, offs.ctypes.data, which.ctypes.data))
-    _last_find = st.as_dict()
-    return offs[:k].tolist(), which[:k].tolist(), [int(x) for x in counts[:np_]]
+    L = load()
+    return _reader_find_call(L.kolm_reader_find_set, L.kolm_reader_find_copy32, h, (pset,), lo, hi, np_, np.uint32, limit)
 
 
 def reader_read_device(h, ranges, dptr: int, cap: int):

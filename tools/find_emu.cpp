@@ -11,42 +11,22 @@
 //   g++ -O2 -std=c++17 -shared -fPIC tools/find_emu.cpp -o find_emu.so
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined tools/find_emu.cpp -o find_emu
 //   ./find_emu        exit status 0 when every case matches the byte-by-byte reference
-#include "../kolmogorovlike-datacompressor_amd/csrc/find_core.h"
+#include "find_emu_common.h"  // Ld (the recording loader), tile_count / tile_emit, find_group, find_grouped, noise
 
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <utility>
-#include <vector>
-
-using namespace fnd;
 
 namespace {
 
-struct Ld {
-    const u8* buf;
-    u32 n;
-    u64 bad = 0, loads = 0;
-    Word operator()(i64 off) {
-        ++loads;
-        const bool ok = (reinterpret_cast<uintptr_t>(buf + off) & (WORD - 1)) == 0 && off < (i64)n && off + (i64)WORD > 0;
-        Word w{{0xA5A5A5A5A5A5A5A5ull, 0xA5A5A5A5A5A5A5A5ull}};
-        if (!ok) {
-            ++bad;
-            return w;
-        }
-        std::memcpy(w.q, buf + off, WORD);
-        return w;
-    }
-};
-
 struct Emu {
+    typedef u8 Which;
     Ld ld;
     u32 lo, shi;
-    Pats P;
+    const Pats& P;
     u32 np;
     u32 mis() const { return (u32)(reinterpret_cast<uintptr_t>(ld.buf) & (WORD - 1)); }
+    u32 cols() const { return np; }
+    u64 cap(u64 stage_bytes) const { return stage_records(stage_bytes, np); }
 
     // one workgroup: pm[i][t] = thread t's mask of pattern i
     void run_tile(u32 tile, u32 pm[MAX_PATTERNS][WG]) {
@@ -58,72 +38,12 @@ struct Emu {
                 pm[i][t] = match_mask(ld, w, mis(), p0, lo, shi, ld.n, P.pre[i], P.mask[i], P.len[i], P.pat[i]);
         }
     }
-    // k_find_count: cnt[col * ntiles + tile]
-    void count(u32 ntiles, std::vector<u32>& cnt) {
-        cnt.assign((size_t)(np + 1) * ntiles, 0);
-        u32 pm[MAX_PATTERNS][WG];
-        for (u32 tile = 0; tile < ntiles; ++tile) {
-            run_tile(tile, pm);
-            for (u32 i = 0; i < np; ++i)
-                for (u32 t = 0; t < WG; ++t) {
-                    const u32 c = (u32)__builtin_popcount(pm[i][t]);
-                    cnt[(size_t)i * ntiles + tile] += c;
-                    cnt[(size_t)np * ntiles + tile] += c;
-                }
-        }
-    }
-    // k_find_emit over tiles [t0, t1): records at tscan[tile] - tscan[t0] + the thread's offset
+    // k_find_count and k_find_emit
+    void count(u32 ntiles, std::vector<u32>& cnt) { tile_count(*this, ntiles, cnt); }
     u64 emit(u32 t0, u32 t1, const u64* tscan, u32* pos, u8* which, u64 cap) {
-        u64 over = 0;
-        u32 pm[MAX_PATTERNS][WG];
-        for (u32 tile = t0; tile < t1; ++tile) {
-            run_tile(tile, pm);
-            u64 slot = tscan[tile] - tscan[t0];
-            for (u32 t = 0; t < WG; ++t)
-                for (u32 j = 0; j < PER; ++j)
-                    for (u32 i = 0; i < np; ++i)
-                        if ((pm[i][t] >> j) & 1u) {
-                            if (slot < cap) pos[slot] = tile * TILE + t * PER + j, which[slot] = (u8)i;
-                            else ++over;
-                            ++slot;
-                        }
-            if (slot != tscan[tile + 1] - tscan[t0]) ++over;  // the count and the emit disagree
-        }
-        return over;
+        return tile_emit(*this, t0, t1, tscan, pos, which, cap);
     }
 };
-
-// One group as the host runs it: count, scan, the emit launches.  Appends (base + position,
-// pattern) to offs / which until `limit` results are held; counts [np] accumulate.
-u64 find_group(const u8* buf, u32 n, u32 lo, u32 shi, const Pats& P, u32 np, u64 base, u64 stage_bytes, u64 limit,
-               u64* counts, std::vector<u64>& offs, std::vector<u8>& which, u32* launches) {
-    Emu e{Ld{buf, n}, lo, shi, P, np};
-    const u32 ntiles = tiles(n);
-    if (!ntiles) return 0;
-    std::vector<u32> cnt;
-    e.count(ntiles, cnt);
-    std::vector<u64> tscan((size_t)ntiles + 1, 0);
-    for (u32 t = 0; t < ntiles; ++t) tscan[t + 1] = tscan[t] + cnt[(size_t)np * ntiles + t];
-    for (u32 i = 0; i < np; ++i)
-        for (u32 t = 0; t < ntiles; ++t) counts[i] += cnt[(size_t)i * ntiles + t];
-    const u64 room = limit > offs.size() ? limit - offs.size() : 0;
-    const u64 want = std::min<u64>(tscan[ntiles], room);
-    const u64 cap = stage_records(stage_bytes, np);
-    std::vector<u32> spos(std::min<u64>(cap, tscan[ntiles]));  // a launch never holds more than either
-    std::vector<u8> swhich(spos.size());
-    u64 got = 0, bad = 0;
-    for (u32 t0 = 0; got < want;) {
-        while (tscan[t0 + 1] == tscan[t0]) ++t0;
-        const u32 t1 = emit_cut(tscan.data(), ntiles, t0, cap, want);
-        bad += e.emit(t0, t1, tscan.data(), spos.data(), swhich.data(), cap);
-        const u64 take = std::min<u64>(tscan[t1] - tscan[t0], want - got);
-        for (u64 k = 0; k < take; ++k) offs.push_back(base + spos[k]), which.push_back(swhich[k]);
-        got += take;
-        t0 = t1;
-        ++*launches;
-    }
-    return bad + e.ld.bad;
-}
 
 bool pats_ok(const u32* pat_off, u32 np) {
     if (np < 1 || np > MAX_PATTERNS) return false;
@@ -146,12 +66,11 @@ extern "C" uint64_t fnd_emu_find(const uint8_t* buf, uint32_t n, uint32_t lo, co
     make_pats(pats, pat_off, np, P);
     std::vector<u64> o;
     std::vector<u8> w;
-    u32 l = 0;
+    *launches = 0;
     for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    const u64 bad = find_group(buf, n, lo, n, P, np, 0, stage_bytes, limit, counts, o, w, &l);
-    *nfound = o.size();
-    *launches = l;
-    for (u64 k = 0; k < o.size() && k < cap; ++k) offs[k] = o[k], which[k] = w[k];
+    Emu e{Ld{buf, n}, lo, n, P, np};
+    const u64 bad = find_group(e, 0, stage_bytes, limit, counts, o, w, launches);
+    hand_out(o, w, offs, which, cap, nfound);
     return bad;
 }
 
@@ -167,10 +86,8 @@ extern "C" void fnd_emu_groups(const uint64_t* bounds, uint32_t ng, uint64_t lo,
     }
 }
 
-// The grouped search as the reader runs it, on the CPU: data is the whole stream, group g its
-// bytes [bounds[g], bounds[g + 1]) (the groups that hold a byte of the window [lo, hi)).
-// Every group's scan buffer is a heap block of exactly the aligned words around
-// [carry][the group's bytes], the carry ending at a 256-byte boundary as on the device.
+// The grouped search as the reader runs it (find_grouped), the aligned words around a scan buffer
+// filled with 0xEE.
 extern "C" uint64_t fnd_emu_find_grouped(const uint8_t* data, const uint64_t* bounds, uint32_t ng, uint64_t lo, uint64_t hi,
                                          const uint8_t* pats, const uint32_t* pat_off, uint32_t np, uint64_t stage_bytes,
                                          uint64_t limit, uint64_t* counts, uint64_t* offs, uint8_t* which, uint64_t cap,
@@ -182,31 +99,17 @@ extern "C" uint64_t fnd_emu_find_grouped(const uint8_t* data, const uint64_t* bo
     for (u32 i = 0; i < np; ++i) L = std::max(L, P.len[i]);
     std::vector<u64> o;
     std::vector<u8> w;
-    u32 l = 0;
-    u64 bad = 0, S = lo;
+    *launches = 0;
     for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    for (u32 g = 0; g < ng; ++g) {
-        const GroupScan gs = group_scan(S, bounds[g], bounds[g + 1], L, g + 1 == ng, hi);
-        const u32 front = (MAX_LEN - gs.carry) & (WORD - 1);  // misalignment of the scan buffer
-        const u64 size = ((u64)front + gs.n + WORD - 1) / WORD * WORD;
-        u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
-        std::memset(raw, 0xEE, size);
-        std::memcpy(raw + front, data + gs.start, gs.n);
-        bad += find_group(raw + front, gs.n, gs.lo, gs.shi, P, np, gs.start, stage_bytes, limit, counts, o, w, &l);
-        std::free(raw);
-        S = gs.S_next;
-    }
-    *nfound = o.size();
-    *launches = l;
-    for (u64 k = 0; k < o.size() && k < cap; ++k) offs[k] = o[k], which[k] = w[k];
+    const u64 bad = find_grouped(data, bounds, ng, lo, hi, L, 0xEE, stage_bytes, limit, counts, o, w, launches,
+                                 [&](const u8* buf, u32 n, u32 glo, u32 shi) { return Emu{Ld{buf, n}, glo, shi, P, np}; });
+    hand_out(o, w, offs, which, cap, nfound);
     return bad;
 }
 
 extern "C" uint32_t fnd_emu_tile_bytes(void) { return TILE; }
 
 namespace {
-
-u64 g_cases = 0;
 
 typedef std::vector<std::pair<u64, u8>> Hits;
 
@@ -222,10 +125,7 @@ Hits reference(const std::vector<u8>& d, u64 lo, u64 hi, const std::vector<std::
 // data at misalignment m in a heap block of exactly the aligned words around it
 int run_case(const std::vector<u8>& d, u32 m, const std::vector<std::vector<u8>>& pats, u64 stage, const char* what) {
     const u32 n = (u32)d.size();
-    const u64 size = ((u64)m + n + WORD - 1) / WORD * WORD;
-    u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
-    std::memset(raw, 0xEE, size);
-    if (n) std::memcpy(raw + m, d.data(), n);
+    u8* raw = aligned_block(d.data(), n, m, 0xEE);
     std::vector<u8> flat;
     std::vector<u32> off{0};
     for (auto& p : pats) flat.insert(flat.end(), p.begin(), p.end()), off.push_back((u32)flat.size());
@@ -244,16 +144,6 @@ int run_case(const std::vector<u8>& d, u32 m, const std::vector<std::vector<u8>>
     std::free(raw);
     ++g_cases;
     return fail;
-}
-
-std::vector<u8> noise(u32 n, u32 seed, u32 letters) {
-    std::vector<u8> d(n);
-    u64 x = 0x9E3779B97F4A7C15ull * (seed + 1);
-    for (u32 i = 0; i < n; ++i) {
-        x ^= x << 13, x ^= x >> 7, x ^= x << 17;
-        d[i] = letters ? (u8)('a' + (x >> 33) % letters) : (u8)(x >> 29);
-    }
-    return d;
 }
 
 }  // namespace

@@ -15,35 +15,15 @@
 //   ./findrx_emu     exit status 0 when every case matches the byte-by-byte reference
 #include "../kolmogorovlike-datacompressor_amd/csrc/findrx_core.h"
 
-#include <algorithm>
+#include "find_emu_common.h"  // Ld (the recording loader), tile_count / tile_emit, find_group, find_grouped, noise
+
 #include <array>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <utility>
-#include <vector>
 
-using namespace fnd;
 using frx::u16;
 
 namespace {
-
-struct Ld {
-    const u8* buf;
-    u32 n;
-    u64 bad = 0, loads = 0;
-    Word operator()(i64 off) {
-        ++loads;
-        const bool ok = (reinterpret_cast<uintptr_t>(buf + off) & (WORD - 1)) == 0 && off < (i64)n && off + (i64)WORD > 0;
-        Word w{{0xA5A5A5A5A5A5A5A5ull, 0xA5A5A5A5A5A5A5A5ull}};
-        if (!ok) {
-            ++bad;
-            return w;
-        }
-        std::memcpy(w.q, buf + off, WORD);
-        return w;
-    }
-};
 
 // a validated automaton: exactly its own entries on the heap
 struct Dfa {
@@ -53,10 +33,13 @@ struct Dfa {
 };
 
 struct Emu {
+    typedef u8 Which;
     Ld ld;
     u32 lo, shi;
     const Dfa& D;
     u32 mis() const { return (u32)(reinterpret_cast<uintptr_t>(ld.buf) & (WORD - 1)); }
+    u32 cols() const { return D.np; }
+    u64 cap(u64 stage_bytes) const { return stage_records(stage_bytes, D.np); }
 
     // one workgroup: the stage, then pm[i][t] = thread t's mask of expression i
     void run_tile(u32 tile, u32 pm[MAX_PATTERNS][WG]) {
@@ -72,72 +55,12 @@ struct Emu {
                 pm[i][t] = frx::match_mask(D.T.data(), D.ncls, stage.data() + mis() + t * PER, p0, lo, shi, ld.n, D.starts[i]);
         }
     }
-    // k_findrx_count: cnt[col * ntiles + tile]
-    void count(u32 ntiles, std::vector<u32>& cnt) {
-        cnt.assign((size_t)(D.np + 1) * ntiles, 0);
-        u32 pm[MAX_PATTERNS][WG];
-        for (u32 tile = 0; tile < ntiles; ++tile) {
-            run_tile(tile, pm);
-            for (u32 i = 0; i < D.np; ++i)
-                for (u32 t = 0; t < WG; ++t) {
-                    const u32 c = (u32)__builtin_popcount(pm[i][t]);
-                    cnt[(size_t)i * ntiles + tile] += c;
-                    cnt[(size_t)D.np * ntiles + tile] += c;
-                }
-        }
-    }
-    // k_findrx_emit over tiles [t0, t1): records at tscan[tile] - tscan[t0] + the thread's offset
+    // k_findrx_count and k_findrx_emit
+    void count(u32 ntiles, std::vector<u32>& cnt) { tile_count(*this, ntiles, cnt); }
     u64 emit(u32 t0, u32 t1, const u64* tscan, u32* pos, u8* which, u64 cap) {
-        u64 over = 0;
-        u32 pm[MAX_PATTERNS][WG];
-        for (u32 tile = t0; tile < t1; ++tile) {
-            run_tile(tile, pm);
-            u64 slot = tscan[tile] - tscan[t0];
-            for (u32 t = 0; t < WG; ++t)
-                for (u32 j = 0; j < PER; ++j)
-                    for (u32 i = 0; i < D.np; ++i)
-                        if ((pm[i][t] >> j) & 1u) {
-                            if (slot < cap) pos[slot] = tile * TILE + t * PER + j, which[slot] = (u8)i;
-                            else ++over;
-                            ++slot;
-                        }
-            if (slot != tscan[tile + 1] - tscan[t0]) ++over;  // the count and the emit disagree
-        }
-        return over;
+        return tile_emit(*this, t0, t1, tscan, pos, which, cap);
     }
 };
-
-// One group as the host runs it: count, scan, the emit launches.  Appends (base + position,
-// expression) to offs / which until `limit` results are held; counts [np] accumulate.
-u64 find_group(const u8* buf, u32 n, u32 lo, u32 shi, const Dfa& D, u64 base, u64 stage_bytes, u64 limit, u64* counts,
-               std::vector<u64>& offs, std::vector<u8>& which, u32* launches) {
-    Emu e{Ld{buf, n}, lo, shi, D};
-    const u32 ntiles = tiles(n), np = D.np;
-    if (!ntiles) return 0;
-    std::vector<u32> cnt;
-    e.count(ntiles, cnt);
-    std::vector<u64> tscan((size_t)ntiles + 1, 0);
-    for (u32 t = 0; t < ntiles; ++t) tscan[t + 1] = tscan[t] + cnt[(size_t)np * ntiles + t];
-    for (u32 i = 0; i < np; ++i)
-        for (u32 t = 0; t < ntiles; ++t) counts[i] += cnt[(size_t)i * ntiles + t];
-    const u64 room = limit > offs.size() ? limit - offs.size() : 0;
-    const u64 want = std::min<u64>(tscan[ntiles], room);
-    const u64 cap = stage_records(stage_bytes, np);
-    std::vector<u32> spos(std::min<u64>(cap, tscan[ntiles]));  // a launch never holds more than either
-    std::vector<u8> swhich(spos.size());
-    u64 got = 0, bad = 0;
-    for (u32 t0 = 0; got < want;) {
-        while (tscan[t0 + 1] == tscan[t0]) ++t0;
-        const u32 t1 = emit_cut(tscan.data(), ntiles, t0, cap, want);
-        bad += e.emit(t0, t1, tscan.data(), spos.data(), swhich.data(), cap);
-        const u64 take = std::min<u64>(tscan[t1] - tscan[t0], want - got);
-        for (u64 k = 0; k < take; ++k) offs.push_back(base + spos[k]), which.push_back(swhich[k]);
-        got += take;
-        t0 = t1;
-        ++*launches;
-    }
-    return bad + e.ld.bad;
-}
 
 // the checks of the library (findrx_check in kolm_reader.cpp), the copies and the hold-back
 bool prepare(const u8* cls, const u16* T, u32 nstates, u32 ncls, const u16* starts, u32 np, Dfa& D) {
@@ -167,20 +90,16 @@ extern "C" uint64_t frx_emu_find(const uint8_t* buf, uint32_t n, uint32_t lo, co
     if (!prepare(cls, T, nstates, ncls, starts, np, D)) return ~0ull;
     std::vector<u64> o;
     std::vector<u8> w;
-    u32 l = 0;
+    *launches = 0;
     for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    const u64 bad = find_group(buf, n, lo, n, D, 0, stage_bytes, limit, counts, o, w, &l);
-    *nfound = o.size();
-    *launches = l;
-    for (u64 k = 0; k < o.size() && k < cap; ++k) offs[k] = o[k], which[k] = w[k];
+    Emu e{Ld{buf, n}, lo, n, D};
+    const u64 bad = find_group(e, 0, stage_bytes, limit, counts, o, w, launches);
+    hand_out(o, w, offs, which, cap, nfound);
     return bad;
 }
 
-// The grouped search as the reader runs it, on the CPU: data is the whole stream, group g its
-// bytes [bounds[g], bounds[g + 1]) (the groups that hold a byte of the window [lo, hi)).  The
-// hold-back is the table's own (frx::hold_back).  Every group's scan buffer is a heap block of
-// exactly the aligned words around [carry][the group's bytes], the carry ending at a 256-byte
-// boundary as on the device; the rest of those words is 0x00.
+// The grouped search as the reader runs it (find_grouped).  The hold-back is the table's own
+// (frx::hold_back); the rest of the aligned words around a scan buffer is 0x00.
 extern "C" uint64_t frx_emu_find_grouped(const uint8_t* data, const uint64_t* bounds, uint32_t ng, uint64_t lo, uint64_t hi,
                                          const uint8_t* cls, const uint16_t* T, uint32_t nstates, uint32_t ncls,
                                          const uint16_t* starts, uint32_t np, uint64_t stage_bytes, uint64_t limit,
@@ -190,23 +109,11 @@ extern "C" uint64_t frx_emu_find_grouped(const uint8_t* data, const uint64_t* bo
     if (!prepare(cls, T, nstates, ncls, starts, np, D)) return ~0ull;
     std::vector<u64> o;
     std::vector<u8> w;
-    u32 l = 0;
-    u64 bad = 0, S = lo;
+    *launches = 0;
     for (u32 i = 0; i < np; ++i) counts[i] = 0;
-    for (u32 g = 0; g < ng; ++g) {
-        const GroupScan gs = group_scan(S, bounds[g], bounds[g + 1], D.L, g + 1 == ng, hi);
-        const u32 front = (MAX_LEN - gs.carry) & (WORD - 1);  // misalignment of the scan buffer
-        const u64 size = ((u64)front + gs.n + WORD - 1) / WORD * WORD;
-        u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
-        std::memset(raw, 0, size);
-        std::memcpy(raw + front, data + gs.start, gs.n);
-        bad += find_group(raw + front, gs.n, gs.lo, gs.shi, D, gs.start, stage_bytes, limit, counts, o, w, &l);
-        std::free(raw);
-        S = gs.S_next;
-    }
-    *nfound = o.size();
-    *launches = l;
-    for (u64 k = 0; k < o.size() && k < cap; ++k) offs[k] = o[k], which[k] = w[k];
+    const u64 bad = find_grouped(data, bounds, ng, lo, hi, D.L, 0, stage_bytes, limit, counts, o, w, launches,
+                                 [&](const u8* buf, u32 n, u32 glo, u32 shi) { return Emu{Ld{buf, n}, glo, shi, D}; });
+    hand_out(o, w, offs, which, cap, nfound);
     return bad;
 }
 
@@ -228,8 +135,6 @@ extern "C" uint32_t frx_emu_tile_bytes(void) { return TILE; }
 extern "C" uint32_t frx_emu_max_entries(void) { return frx::MAX_ENTRIES; }
 
 namespace {
-
-u64 g_cases = 0;
 
 typedef std::vector<std::pair<u64, u8>> Hits;
 
@@ -318,10 +223,7 @@ Built build(const std::vector<Expr>& es) {
 // data at misalignment m in a heap block of exactly the aligned words around it, zeros around the data
 int run_case(const std::vector<u8>& d, u32 m, const std::vector<Expr>& es, u64 stage, const char* what) {
     const u32 n = (u32)d.size();
-    const u64 size = ((u64)m + n + WORD - 1) / WORD * WORD;
-    u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
-    std::memset(raw, 0, size);
-    if (n) std::memcpy(raw + m, d.data(), n);
+    u8* raw = aligned_block(d.data(), n, m, 0);
     const Built B = build(es);
     const Hits want = reference(d, es);
     std::vector<u64> counts(es.size()), offs(want.size() + 1);
@@ -338,16 +240,6 @@ int run_case(const std::vector<u8>& d, u32 m, const std::vector<Expr>& es, u64 s
     std::free(raw);
     ++g_cases;
     return fail;
-}
-
-std::vector<u8> noise(u32 n, u32 seed, u32 letters) {
-    std::vector<u8> d(n);
-    u64 x = 0x9E3779B97F4A7C15ull * (seed + 1);
-    for (u32 i = 0; i < n; ++i) {
-        x ^= x << 13, x ^= x >> 7, x ^= x << 17;
-        d[i] = letters ? (u8)('a' + (x >> 33) % letters) : (u8)(x >> 29);
-    }
-    return d;
 }
 
 Cls range(u32 a, u32 b) {

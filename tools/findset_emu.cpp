@@ -5,17 +5,18 @@
 // per-tile totals and per-pattern counters, the exclusive scan of the tile totals, the emit
 // launches cut at scanned tile boundaries so that each fits the staging array -- behind a C
 // interface for tests/test_findset_core.py, and a main() that runs the sweeps on its own.  The data
-// goes through find_emu.cpp's recording loader (every load checked against the load contract, on
+// goes through find_emu_common.h's recording loader (every load checked against the load contract, on
 // heap buffers of exactly the aligned words it allows); the set's tables are heap vectors of
 // exact size, so under -fsanitize=address,undefined a probe, a bucket walk or a tail compare that
 // leaves them is an error.
 //   g++ -O2 -std=c++17 -shared -fPIC tools/findset_emu.cpp -o findset_emu.so
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined tools/findset_emu.cpp -o findset_emu
 //   ./findset_emu     exit status 0 when every case matches the byte-by-byte reference
-#define FND_EMU_NO_MAIN 1
-#include "find_emu.cpp"  // Ld (the recording loader), noise, g_cases
-
 #include "../kolmogorovlike-datacompressor_amd/csrc/findset_core.h"
+#include "find_emu_common.h"  // Ld (the recording loader), find_group, find_grouped, noise, g_cases
+
+#include <cstdio>
+#include <utility>
 
 namespace {
 
@@ -25,10 +26,14 @@ struct SetEmu {
 };
 
 struct FsEmu {
+    typedef u32 Which;
     Ld ld;
     u32 lo, shi;
     const fst::Set& S;
+    u64* pcnt;  // the per-pattern counters of the call
     u32 mis() const { return (u32)(reinterpret_cast<uintptr_t>(ld.buf) & (WORD - 1)); }
+    u32 cols() const { return 0; }  // k_find_scan with np = 0: cnt holds the tile totals only
+    u64 cap(u64 stage_bytes) const { return fst::stage_records(stage_bytes, S.np); }
 
     // one thread of one tile: f(position, entry) for its matches, positions ascending
     template <class F>
@@ -43,7 +48,7 @@ struct FsEmu {
         return c;
     }
     // k_findset_count: the workgroups walk their spans
-    void count(u32 ntiles, std::vector<u32>& cnt, u64* pcnt) {
+    void count(u32 ntiles, std::vector<u32>& cnt) {
         cnt.assign(ntiles, 0);
         const u32 span = fst::span_tiles(S.filter_words * 4);
         for (u32 wg = 0; wg < fst::spans(ntiles, span); ++wg)
@@ -69,44 +74,11 @@ struct FsEmu {
     }
 };
 
-// One group as the host runs it (findset_group and emit_matches of kolm_reader.cpp).
-u64 fs_group(const u8* buf, u32 n, u32 lo, u32 shi, const fst::Set& S, u64 base, u64 stage_bytes, u64 limit, u64* pcnt,
-             std::vector<u64>& offs, std::vector<u32>& which, u32* launches) {
-    FsEmu e{Ld{buf, n}, lo, shi, S};
-    const u32 ntiles = tiles(n);
-    if (!ntiles) return 0;
-    std::vector<u32> cnt;
-    e.count(ntiles, cnt, pcnt);
-    std::vector<u64> tscan((size_t)ntiles + 1, 0);
-    for (u32 t = 0; t < ntiles; ++t) tscan[t + 1] = tscan[t] + cnt[t];
-    const u64 room = limit > offs.size() ? limit - offs.size() : 0;
-    const u64 want = std::min<u64>(tscan[ntiles], room);
-    const u64 cap = fst::stage_records(stage_bytes, S.np);
-    std::vector<u32> spos(std::min<u64>(cap, tscan[ntiles])), swhich(spos.size());  // exact: ASan sees a slot past them
-    u64 got = 0, bad = 0;
-    for (u32 t0 = 0; got < want;) {
-        while (tscan[t0 + 1] == tscan[t0]) ++t0;
-        const u32 t1 = emit_cut(tscan.data(), ntiles, t0, cap, want);
-        bad += e.emit(t0, t1, tscan.data(), spos.data(), swhich.data(), spos.size());
-        const u64 take = std::min<u64>(tscan[t1] - tscan[t0], want - got);
-        for (u64 k = 0; k < take; ++k) offs.push_back(base + spos[k]), which.push_back(swhich[k]);
-        got += take;
-        t0 = t1;
-        ++*launches;
-    }
-    return bad + e.ld.bad;
-}
-
 bool set_args_ok(const u32* pat_off, u32 np) {
     if (np < 1 || np > fst::MAX_PATTERNS) return false;
     for (u32 i = 0; i < np; ++i)
         if (pat_off[i + 1] <= pat_off[i] || pat_off[i + 1] - pat_off[i] > MAX_LEN) return false;
     return true;
-}
-
-void hand_out(const std::vector<u64>& o, const std::vector<u32>& w, u64* offs, u32* which, u64 cap, u64* nfound) {
-    *nfound = o.size();
-    for (u64 k = 0; k < o.size() && k < cap; ++k) offs[k] = o[k], which[k] = w[k];
 }
 
 }  // namespace
@@ -170,39 +142,26 @@ extern "C" uint64_t fst_emu_find(const void* hv, const uint8_t* buf, uint32_t n,
     const SetEmu* h = static_cast<const SetEmu*>(hv);
     std::vector<u64> o;
     std::vector<u32> w;
-    u32 l = 0;
+    *launches = 0;
     std::fill(counts, counts + h->S.np, 0);
-    const u64 bad = fs_group(buf, n, lo, n, h->S, 0, stage_bytes, limit, counts, o, w, &l);
-    *launches = l;
+    FsEmu e{Ld{buf, n}, lo, n, h->S, counts};
+    const u64 bad = find_group(e, 0, stage_bytes, limit, counts, o, w, launches);
     hand_out(o, w, offs, which, cap, nfound);
     return bad;
 }
 
-// The grouped search as the reader runs it: data is the whole stream, group g its bytes
-// [bounds[g], bounds[g + 1]).  Every group's scan buffer is a heap block of exactly the aligned
-// words around [carry][the group's bytes], the carry ending at a 256-byte boundary as on the device.
+// The grouped search as the reader runs it (find_grouped), the aligned words around a scan buffer
+// filled with 0xEE.
 extern "C" uint64_t fst_emu_find_grouped(const void* hv, const uint8_t* data, const uint64_t* bounds, uint32_t ng, uint64_t lo,
                                          uint64_t hi, uint64_t stage_bytes, uint64_t limit, uint64_t* counts, uint64_t* offs,
                                          uint32_t* which, uint64_t cap, uint64_t* nfound, uint32_t* launches) {
     const SetEmu* h = static_cast<const SetEmu*>(hv);
-    const u32 L = h->T.info.L;
     std::vector<u64> o;
     std::vector<u32> w;
-    u32 l = 0;
-    u64 bad = 0, S = lo;
+    *launches = 0;
     std::fill(counts, counts + h->S.np, 0);
-    for (u32 g = 0; g < ng; ++g) {
-        const GroupScan gs = group_scan(S, bounds[g], bounds[g + 1], L, g + 1 == ng, hi);
-        const u32 front = (MAX_LEN - gs.carry) & (WORD - 1);  // misalignment of the scan buffer
-        const u64 size = ((u64)front + gs.n + WORD - 1) / WORD * WORD;
-        u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
-        std::memset(raw, 0xEE, size);
-        std::memcpy(raw + front, data + gs.start, gs.n);
-        bad += fs_group(raw + front, gs.n, gs.lo, gs.shi, h->S, gs.start, stage_bytes, limit, counts, o, w, &l);
-        std::free(raw);
-        S = gs.S_next;
-    }
-    *launches = l;
+    const u64 bad = find_grouped(data, bounds, ng, lo, hi, h->T.info.L, 0xEE, stage_bytes, limit, counts, o, w, launches,
+                                 [&](const u8* buf, u32 n, u32 glo, u32 shi) { return FsEmu{Ld{buf, n}, glo, shi, h->S, counts}; });
     hand_out(o, w, offs, which, cap, nfound);
     return bad;
 }
@@ -228,10 +187,7 @@ SetHits set_reference(const std::vector<u8>& d, const PatList& pats) {
 int run_set_case(const std::vector<u8>& d, u32 m, const PatList& pats, u64 stage, const char* what, u32 min_launches = 0,
                  const SetHits* want_in = nullptr) {
     const u32 n = (u32)d.size();
-    const u64 size = ((u64)m + n + WORD - 1) / WORD * WORD;
-    u8* raw = (u8*)std::aligned_alloc(WORD, size ? size : WORD);
-    std::memset(raw, 0xEE, size);
-    if (n) std::memcpy(raw + m, d.data(), n);
+    u8* raw = aligned_block(d.data(), n, m, 0xEE);
     std::vector<u8> flat;
     std::vector<u32> off{0};
     for (auto& p : pats) flat.insert(flat.end(), p.begin(), p.end()), off.push_back((u32)flat.size());
